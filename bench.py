@@ -1,6 +1,6 @@
 """GAT-stack edges/sec (fwd+bwd) on the synthetic 1k-camera / 200k-point scene (BASELINE config 4).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
 
 A step = one forward + backward of the full GraphAttnSfMNet (12 blocks, learning
@@ -10,7 +10,14 @@ are resident in HBM before timing.  value = E * K / (max over ranks of the
 timed wall time).  With N > 1 the scene's points are sharded over the ranks
 (gasfm_amd.distributed) — strong scaling: the scene is fixed.
 
-Also reported, on the same line:
+A plain run sets up, warms up, times the K steps and prints the result line.  --dump-outputs DIR
+then writes what the last timed step returned to its caller (the loss, the two predictions, every
+parameter's gradient) as DIR/<name>.npy (float32, 56 MiB at most: the predictions whole, the large
+gradients as a seeded sample; DIR/manifest.json lists them).  The scene, the
+weights and the loss coefficients are seeded, so two builds run with the same arguments are
+comparable output for output.
+
+With --full, also reported on the same line (each takes runs of its own after the timed region):
   roofline      the step's dominant kernel: the fused camera-attention + edge-prologue
                 backward (edge_cam_pbwd_kernel<LN,RES>, ~23 % of the step), timed live with
                 HIP events around each of its launches on its stream right after the timed
@@ -187,6 +194,116 @@ def cpu_baseline(sample_scale, threads, reps=4):
                       f"stands for config 4 (linear in E: profiles/r2_cpu_baseline_scaling.json)"}
 
 
+def measure_rooflines(data, fwd_bwd):
+    """--full: the two roofline records, from 2 eager steps (events cannot be read out of a replayed
+    graph) run after the timed region."""
+    from gasfm_amd import attention
+    # roofline kernel: the point-direction attention forward, in eager steps right after the
+    # timed region (events cannot be read out of a replayed graph): events around each of its
+    # launches (mean_us: matches rocprof's in-step durations), plus 20 back-to-back re-launches
+    # on the inputs of its last launch (mean_us_back_to_back: cache-warm, informational)
+    timer = attention.KernelTimer(lambda tag, HC: tag == "proj2scenepoint" and HC == 32, hold_cycles=HOLD_CYCLES)
+    attention.KERNEL_TIMER = timer
+    timer.enabled = True
+    # the dominant kernel: edge_cam_pbwd with LayerNorm and the residual term (blocks 1..11); with the
+    # epilogue fold, its launches that carry both epilogue parts (blocks 2..11)
+    from gasfm_amd import edge_block
+    fold = edge_block.EPI_FOLD
+    pbwd = LaunchTimer("edge_cam_pbwd", lambda *a, **k: a[1] is not None and a[7] is not None
+                       and (not fold or (k.get("epi") is not None and k.get("dwp") is not None)))
+    flop_e = PBWD_FOLD_FLOP_PER_EDGE if fold else PBWD_FLOP_PER_EDGE
+    bytes_e = PBWD_FOLD_BYTES_PER_EDGE if fold else PBWD_BYTES_PER_EDGE
+    # (round 4: the EPI template argument is an int -- 1 the 32-wide fold, 2 block 0's -- so newer
+    # tables print it as a number)
+    pbwd_name = (("edge_cam_pbwd_kernel<true, true, 1, true>", "edge_cam_pbwd_kernel<true, true, true, true>") if fold
+                 else ("edge_cam_pbwd_kernel<true, true, 0, false>", "edge_cam_pbwd_kernel<true, true, false, false>"))
+    for _ in range(2):
+        fwd_bwd()
+    timer.enabled = False
+    attention.KERNEL_TIMER = None
+    pbwd_ms = pbwd.close()
+    pbwd_launches = len(pbwd.events)
+    e_cam = data.graph_wrappers["proj2view"].plan.num_edges
+    pbwd_tfs = flop_e * e_cam / (pbwd_ms * 1e-3) / 1e12 if pbwd_ms else None
+    pbwd_gbs = bytes_e * e_cam / (pbwd_ms * 1e-3) / 1e9 if pbwd_ms else None
+    pbwd_traffic = pmc_kernel_traffic(pbwd_name, e_cam)
+    kern_ms = timer.mean_ms()
+    b2b_ms = timer.replay_ms(20)
+    plan = data.graph_wrappers["proj2scenepoint"].plan
+    e_local = plan.num_edges
+    n_local = plan.num_targets
+    bytes_per_launch = attn_fwd_bytes(e_local, n_local, 4, 32, bool(timer.gathered))
+    achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9 if kern_ms else None
+    return {
+        "roofline": {"kernel": pbwd_name[0] + ": camera-attention + edge-prologue backward"
+                               + (" + the edge epilogue's backward (dSv, dP0 of the previous block, dWp of this "
+                                  "one)" if fold else "") + " (the step's largest kernel), per launch",
+                     "bound": "mfma", "achieved": pbwd_tfs, "peak": MFMA_F32_PEAK_TFS, "unit": "TFLOP/s",
+                     "frac": (pbwd_tfs / MFMA_F32_PEAK_TFS) if pbwd_tfs else None,
+                     "traffic": pbwd_traffic,
+                     "traffic_source": f"profiles/{os.path.basename(PMC_KERNELS)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
+                                       "passes of this bench, per launch"
+                                       + (f"; {pbwd_traffic / (bytes_e * e_cam):.2f}x the algorithmic bytes)"
+                                          if pbwd_traffic else "; not taken on this workload)"),
+                     "flop_per_launch": flop_e * e_cam,
+                     "algorithmic_bytes": bytes_e * e_cam,
+                     "hbm_achieved_GBps": pbwd_gbs,
+                     "hbm_frac": (pbwd_gbs / HBM_PEAK_GBS) if pbwd_gbs else None,
+                     "mean_us": pbwd_ms * 1e3 if pbwd_ms else None, "launches_timed": pbwd_launches,
+                     "timing": "HIP events on the launch stream around each of its launches in 2 eager steps "
+                               "after the timed region, the stream held by a spin kernel while the events and "
+                               "the launch are enqueued (the host's enqueue latency is not timed; agrees with "
+                               "the rocprof durations inside the replayed step)"},
+        "roofline_attention": {"kernel": "attn_fwd_grp_kernel<4,1> point direction (proj2scenepoint), per launch",
+                     "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+                     "traffic": pmc_traffic(e_local, n_local),
+                     "traffic_source": "profiles/r2_pmc_attn_fwd.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
+                                       "passes of this bench, per launch)",
+                     "algorithmic_bytes": bytes_per_launch, "mean_us": kern_ms * 1e3 if kern_ms else None,
+                     "mean_us_back_to_back": b2b_ms * 1e3 if b2b_ms else None,
+                     "launches_timed": len(timer.events),
+                     "timing": "HIP events on the launch stream around each of its launches in 2 eager steps "
+                               "after the timed region, the stream held by a spin kernel while the events and "
+                               "the launch are enqueued (mean_us; agrees with the rocprof durations inside the "
+                               "replayed step); mean_us_back_to_back: 20 re-launches on the inputs of its last "
+                               "launch between two events (cache-warm, not used for achieved)"},
+    }
+
+
+DUMP_BUDGET_BYTES = 56 * 2 ** 20  # --dump-outputs writes at most this much (float32 elements x 4)
+DUMP_WHOLE = 1 << 16  # arrays up to this many elements are always written whole
+
+
+def dump_outputs(out_dir, arrays, suffix="", whole=()):
+    """Write name -> tensor as out_dir/<name><suffix>.npy (float32).  When everything together would
+    exceed DUMP_BUDGET_BYTES, every array above DUMP_WHOLE elements that is not named in ``whole``
+    is cut to the same fraction of its elements, at flat indices drawn from default_rng(0) (sorted;
+    the same for equal sizes in every run); manifest<suffix>.json records shape, elements kept and
+    the sampling."""
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = {k: int(v.numel()) for k, v in arrays.items()}
+    budget = DUMP_BUDGET_BYTES // 4
+    small = sum(n for k, n in sizes.items() if n <= DUMP_WHOLE or k in whole)
+    large = sum(sizes.values()) - small
+    frac = 1.0 if (small + large <= budget or large == 0) else max(0.0, (budget - small) / large)
+    manifest = {}
+    for k, v in arrays.items():
+        a = v.detach().to(torch.float32).cpu().numpy()
+        n = sizes[k]
+        keep = n if (frac >= 1.0 or n <= DUMP_WHOLE or k in whole) else int(n * frac)
+        if keep < n:
+            idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+            a = np.ascontiguousarray(a.reshape(-1)[idx])
+        name = k.replace("/", "_") + suffix
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        manifest[name] = {"shape": list(v.shape), "elements": n, "written": keep,
+                          "sample": None if keep == n else
+                          "flat indices sort(default_rng(0).choice(elements, written, replace=False))"}
+    with open(os.path.join(out_dir, "manifest" + suffix + ".json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -231,7 +348,13 @@ def main():
     ap.add_argument("--m", "--cameras", dest="m", type=int, default=1000)
     ap.add_argument("--n", "--points", dest="n", type=int, default=200_000)
     ap.add_argument("--layers", type=int, default=12)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline kernels (eager steps with HIP events) "
+                         "and the CPU baseline, and report them on the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, Ps_norm, pts3D, parameter gradients) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python (no hipGraph)")
     ap.add_argument("--cpu-sample-scale", type=float, default=0.1)
     ap.add_argument("--proj-precision", choices=("fp32", "bf16"), default="fp32",
@@ -251,6 +374,8 @@ def main():
                     help="per-rank proxy: rank 0's shard of a W-GPU step on this one GPU, collectives replaced by "
                          "local copies (timing of the per-rank compute; numerically meaningless)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -275,7 +400,7 @@ def main():
         log(f"[rank {rank}] process group up (world {world})")
 
     import gasfm_amd
-    from gasfm_amd import attention, synthetic
+    from gasfm_amd import synthetic
 
     t0 = time.time()
     sc = synthetic.windowed_scene(args.m, args.n, seed=4)
@@ -300,8 +425,12 @@ def main():
 
     cx = cX if not (dist_on or emul) else cX[:, data.point_slice].contiguous()
 
+    last_pred = {}  # --dump-outputs: the predictions of the latest step (in a replayed graph: its static outputs)
+
     def fwd_bwd():
         pred = model(data)
+        if args.dump_outputs:
+            last_pred.update((k, pred[k].detach()) for k in ("Ps_norm", "pts3D"))
         # replicated outputs enter every rank's loss in full, local points once (distributed.py)
         loss = (pred["Ps_norm"] * cP).sum() + (pred["pts3D"] * cx).sum()
         loss.backward()
@@ -316,10 +445,10 @@ def main():
             for p in model.parameters():
                 p.grad = None
 
-        def step():
-            fwd_bwd()
+        def step():  # as CapturedStep: returns the loss, leaves this step's gradients in p.grad
             for p in model.parameters():
                 p.grad = None
+            return fwd_bwd()
         execution = "eager (one Python/autograd launch per kernel)"
     else:
         # warm-up steps run inside CapturedStep (before capture); every timed step replays
@@ -340,7 +469,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        loss = step()
     torch.cuda.synchronize()
     if dist_on:
         torch.distributed.barrier()
@@ -349,46 +478,22 @@ def main():
         t = torch.tensor([dt], device=dev if args.backend == "nccl" else "cpu")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
-    # roofline kernel: the point-direction attention forward, in eager steps right after the
-    # timed region (events cannot be read out of a replayed graph): events around each of its
-    # launches (mean_us: matches rocprof's in-step durations), plus 20 back-to-back re-launches
-    # on the inputs of its last launch (mean_us_back_to_back: cache-warm, informational)
-    timer = attention.KernelTimer(lambda tag, HC: tag == "proj2scenepoint" and HC == 32, hold_cycles=HOLD_CYCLES)
-    attention.KERNEL_TIMER = timer
-    timer.enabled = True
-    # the dominant kernel: edge_cam_pbwd with LayerNorm and the residual term (blocks 1..11); with the
-    # epilogue fold, its launches that carry both epilogue parts (blocks 2..11)
-    from gasfm_amd import edge_block
-    fold = edge_block.EPI_FOLD
-    pbwd = LaunchTimer("edge_cam_pbwd", lambda *a, **k: a[1] is not None and a[7] is not None
-                       and (not fold or (k.get("epi") is not None and k.get("dwp") is not None)))
-    flop_e = PBWD_FOLD_FLOP_PER_EDGE if fold else PBWD_FLOP_PER_EDGE
-    bytes_e = PBWD_FOLD_BYTES_PER_EDGE if fold else PBWD_BYTES_PER_EDGE
-    # (round 4: the EPI template argument is an int -- 1 the 32-wide fold, 2 block 0's -- so newer
-    # tables print it as a number)
-    pbwd_name = (("edge_cam_pbwd_kernel<true, true, 1, true>", "edge_cam_pbwd_kernel<true, true, true, true>") if fold
-                 else ("edge_cam_pbwd_kernel<true, true, 0, false>", "edge_cam_pbwd_kernel<true, true, false, false>"))
-    for _ in range(2):
-        fwd_bwd()
-    timer.enabled = False
-    attention.KERNEL_TIMER = None
-    pbwd_ms = pbwd.close()
-    pbwd_launches = len(pbwd.events)
-    e_cam = data.graph_wrappers["proj2view"].plan.num_edges
-    pbwd_tfs = flop_e * e_cam / (pbwd_ms * 1e-3) / 1e12 if pbwd_ms else None
-    pbwd_gbs = bytes_e * e_cam / (pbwd_ms * 1e-3) / 1e9 if pbwd_ms else None
-    pbwd_traffic = pmc_kernel_traffic(pbwd_name, e_cam)
-    kern_ms = timer.mean_ms()
-    b2b_ms = timer.replay_ms(20)
-    plan = data.graph_wrappers["proj2scenepoint"].plan
-    e_local = plan.num_edges
-    n_local = plan.num_targets
-    bytes_per_launch = attn_fwd_bytes(e_local, n_local, 4, 32, bool(timer.gathered))
-    achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9 if kern_ms else None
+    if args.dump_outputs:
+        # what the caller of the timed step holds after the last one: the returned loss, the
+        # predictions, and every parameter's gradient in p.grad (rank r > 0 writes <name>.rank<r>.npy)
+        arrays = {"loss": loss.detach().reshape(1), **last_pred}
+        arrays.update(("grad." + k, p.grad) for k, p in model.named_parameters() if p.grad is not None)
+        dump_outputs(args.dump_outputs, arrays, suffix="" if rank == 0 else f".rank{rank}", whole=tuple(last_pred))
+    roofs = {}
+    if args.full:
+        if args.eager:  # the eager step leaves its gradients in place; the steps below start from none
+            for p in model.parameters():
+                p.grad = None
+        roofs = measure_rooflines(data, fwd_bwd)
 
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.cpu_sample_scale, host_threads())
         res = {
             "metric": "GAT-stack edges/sec (fwd+bwd) on cam/point scene graph; 1/2/4/8 MI355X",
@@ -416,41 +521,9 @@ def main():
                                        + ("" if args.backend == "nccl" else
                                           " (gloo on one GPU: a functional test of the N-rank path, not a measurement)")
                                        if dist_on else "single GPU")},
-            "roofline": {"kernel": pbwd_name[0] + ": camera-attention + edge-prologue backward"
-                                   + (" + the edge epilogue's backward (dSv, dP0 of the previous block, dWp of this "
-                                      "one)" if fold else "") + " (the step's largest kernel), per launch",
-                         "bound": "mfma", "achieved": pbwd_tfs, "peak": MFMA_F32_PEAK_TFS, "unit": "TFLOP/s",
-                         "frac": (pbwd_tfs / MFMA_F32_PEAK_TFS) if pbwd_tfs else None,
-                         "traffic": pbwd_traffic,
-                         "traffic_source": f"profiles/{os.path.basename(PMC_KERNELS)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
-                                           "passes of this bench, per launch"
-                                           + (f"; {pbwd_traffic / (bytes_e * e_cam):.2f}x the algorithmic bytes)"
-                                              if pbwd_traffic else "; not taken on this workload)"),
-                         "flop_per_launch": flop_e * e_cam,
-                         "algorithmic_bytes": bytes_e * e_cam,
-                         "hbm_achieved_GBps": pbwd_gbs,
-                         "hbm_frac": (pbwd_gbs / HBM_PEAK_GBS) if pbwd_gbs else None,
-                         "mean_us": pbwd_ms * 1e3 if pbwd_ms else None, "launches_timed": pbwd_launches,
-                         "timing": "HIP events on the launch stream around each of its launches in 2 eager steps "
-                                   "after the timed region, the stream held by a spin kernel while the events and "
-                                   "the launch are enqueued (the host's enqueue latency is not timed; agrees with "
-                                   "the rocprof durations inside the replayed step)"},
-            "roofline_attention": {"kernel": "attn_fwd_grp_kernel<4,1> point direction (proj2scenepoint), per launch",
-                         "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-                         "traffic": pmc_traffic(e_local, n_local),
-                         "traffic_source": "profiles/r2_pmc_attn_fwd.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
-                                           "passes of this bench, per launch)",
-                         "algorithmic_bytes": bytes_per_launch, "mean_us": kern_ms * 1e3 if kern_ms else None,
-                         "mean_us_back_to_back": b2b_ms * 1e3 if b2b_ms else None,
-                         "launches_timed": len(timer.events),
-                         "timing": "HIP events on the launch stream around each of its launches in 2 eager steps "
-                                   "after the timed region, the stream held by a spin kernel while the events and "
-                                   "the launch are enqueued (mean_us; agrees with the rocprof durations inside the "
-                                   "replayed step); mean_us_back_to_back: 20 re-launches on the inputs of its last "
-                                   "launch between two events (cache-warm, not used for achieved)"},
+            **roofs,
             "execution": execution,
-            "cpu_baseline": cpu,
+            **({"cpu_baseline": cpu} if args.full else {}),
         }
         print(json.dumps(res), flush=True)
     if dist_on:

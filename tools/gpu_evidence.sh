@@ -3,13 +3,15 @@
 # and its breakdown.  Usage: tools/gpu_evidence.sh TAG (outputs in gpurun_out/ as TAG_*).
 TAG=${1:-ev}
 set -o pipefail
+OUT=${OUT:-bench_out}  # where the default bench line goes
+mkdir -p $OUT
 mkdir -p gpurun_out
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > gpurun_out/${TAG}_gpu_tests.log 2>&1 || { grep -B5 -A30 "^E \|FAILED" gpurun_out/${TAG}_gpu_tests.log | head -80; tail -3 gpurun_out/${TAG}_gpu_tests.log; exit 1; }
 tail -1 gpurun_out/${TAG}_gpu_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1 || { tail -30 gpurun_out/${TAG}_smoke.log; exit 1; }
 tail -1 gpurun_out/${TAG}_smoke.log
-SECONDS=0; timeout -k 10 600 python bench.py > gpurun_out/${TAG}_bench_default.json 2> gpurun_out/${TAG}_bench_default.err || { tail -30 gpurun_out/${TAG}_bench_default.err; exit 1; }
-tail -1 gpurun_out/${TAG}_bench_default.json | cut -c1-400
+SECONDS=0; timeout -k 10 600 python bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err || { tail -30 $OUT/${TAG}_bench_default.err; exit 1; }
+tail -1 $OUT/${TAG}_bench_default.json | cut -c1-400
 echo "bench wall: ${SECONDS}s"
 bash tools/prof_full.sh ${TAG} > gpurun_out/${TAG}_prof.txt 2>&1 || { tail -20 gpurun_out/${TAG}_prof.txt; exit 1; }
 head -8 gpurun_out/pf_${TAG}_breakdown.txt
