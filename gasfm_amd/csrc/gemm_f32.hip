@@ -290,8 +290,10 @@ __global__ __launch_bounds__(64 * NWV) void gemm_f32_d_kernel(int M, int N, int 
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = f32x4f{0.f, 0.f, 0.f, 0.f};
+  if (nk > 0) {  // K == 0: no chunk to clamp to (A / B may be null), C = Cin + bias
 #pragma unroll
-  for (int s = 0; s < DS - 1; ++s) issue(s);
+    for (int s = 0; s < DS - 1; ++s) issue(s);
+  }
   const int fr = lane & 15, fq = lane >> 4;
   for (int t = 0; t < nk; ++t) {
     // chunk t landed for this wave (DS - 2 younger chunks may still fly), then for every wave

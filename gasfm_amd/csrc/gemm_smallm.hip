@@ -15,9 +15,10 @@
 //   mode 0  C[M,N] = A[M,K] W[N,K]^T (+ bias[N]) (+ Cin[M,N])   y = x W^T (+ b) (+ skip)
 //   mode 1  C[M,N] = A[M,K] W[K,N]                               dx = dy W
 //   mode 2  C[I,J] = A[K,I]^T B[K,J]                             dW = dy^T x  (K = rows, small)
-// Modes 0 / 1 need K % (16 x 8 K-slices) == 0 and N % 32 == 0 (M arbitrary); mode 2 needs
-// I % 16 == 0, J % 128 == 0 and K <= 256 (rows past K read as 0).  Exact fp32 products, fp32 sums in a fixed
-// order.
+// Modes 0 / 1 need K % (16 x 8 K-slices) == 0 with K / 128 one of 1, 2, 4, 8, 16 (the instantiated
+// per-wave step counts: K <= 2048) and N % 32 == 0 (M >= 0 arbitrary); mode 2 needs I % 16 == 0,
+// J % 128 == 0 and 1 <= K <= 256 (rows past K read as 0).  N, K >= 1 in every mode.  Exact fp32
+// products, fp32 sums in a fixed order.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

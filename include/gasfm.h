@@ -975,8 +975,8 @@ int gasfm_gemm_f32(int32_t M, int32_t N, int32_t K, const float* A, int64_t sAm,
  *   mode 0  C[M,N] = A[M,K] W[N,K]^T (+ bias[N]) (+ Cin[M,N]); A, W row-major (lda, ldb)
  *   mode 1  C[M,N] = A[M,K] W[K,N]; bias / Cin must be null
  *   mode 2  C[M,N] = A[K,M]^T B[K,N] (K: rows, any); bias / Cin must be null
- * gasfm_gemm_f32_smallm_ok says whether (mode, M, N, K) is supported (modes 0 / 1: K % 64 == 0,
- * N % 32 == 0; mode 2: M % 16 == 0, N % 128 == 0).  Cin may alias C. */
+ * gasfm_gemm_f32_smallm_ok says whether (mode, M, N, K) is supported (modes 0 / 1: K = 128, 256,
+ * 512, 1024 or 2048, N % 32 == 0; mode 2: M % 16 == 0, N % 128 == 0, K <= 256).  Cin may alias C. */
 int32_t gasfm_gemm_f32_smallm_ok(int32_t mode, int32_t M, int32_t N, int32_t K);
 int gasfm_gemm_f32_smallm(int32_t mode, int32_t M, int32_t N, int32_t K, const float* A, int64_t lda, const float* B,
                           int64_t ldb, const float* bias, const float* Cin, int64_t ldCin, float* C, int64_t ldC,

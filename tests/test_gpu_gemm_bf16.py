@@ -13,6 +13,7 @@ Two references per case:
 import pytest
 import torch
 
+import gemm_checks
 from gasfm_amd import _native
 
 pytestmark = pytest.mark.gpu
@@ -99,3 +100,76 @@ def test_deterministic(device):
     c1 = _native.gemm_bf16(a, b)
     c2 = _native.gemm_bf16(a, b)
     assert torch.equal(c1, c2)
+
+
+# ---- tile edges, strides, K = 0: every call through gemm_checks' guarded output ----------------
+# 64 x 64 tile, K step 64, 8-XCD remap, M-tiles in groups of 4.  (M, N, K): ntm x ntn tiles
+EDGE = [(300, 1028, 260),  # 5 x 17 = 85: no remap, ragged last M-group, N % 64 = 4, K % 64 = 4
+        (380, 760, 68),    # 6 x 12 = 72: remap with a ragged M-group
+        (64, 64, 4),       # one full tile, one K step clamped at k = 0
+        (68, 132, 60),     # 2 x 3 tiles, 4 rows / 4 columns in the last ones
+        (128, 64, 64)]     # full tiles, one full K step
+
+
+def _gen(*key):
+    return torch.Generator(device="cpu").manual_seed(sum(k * p for k, p in zip(key, (7, 131, 1009, 5))))
+
+
+def _normwise(a, b):
+    """The existing 1e-2 normwise check against the product of the UNROUNDED operands."""
+    p32 = a.double() @ b.double()
+
+    def after(C, cin, bias):
+        ref32 = p32
+        if cin is not None:
+            ref32 = ref32 + cin.double()
+        if bias is not None:
+            ref32 = ref32 + bias.double()
+        rel = (C.double() - ref32).norm() / ref32.norm().clamp_min(1e-30)
+        assert rel <= 1e-2, f"normwise vs fp32 product {rel:.3e}"
+    return after
+
+
+def _run(form, M, N, K, device, tag=0, strided_a=False):
+    g = _gen(M, N, K, gemm_checks.FORMS.index(form) + tag)
+    a, b = gemm_checks.operands(form, M, N, K, g, device, strided_a=strided_a)
+    gemm_checks.run_epilogues(_native.gemm_bf16, a, b, g, round_operands=True, after=_normwise(a, b))
+
+
+@pytest.mark.parametrize("M,N,K", EDGE)
+@pytest.mark.parametrize("form", gemm_checks.FORMS)
+def test_tile_edges(device, form, M, N, K):
+    """gemm_bf16_kernel<AM, BN_> = <0,0> fwd, <0,1> dgrad, <1,1> wgrad, <1,0> mixed (P.t() @ W.t())."""
+    _run(form, M, N, K, device)
+
+
+@pytest.mark.parametrize("K", [1, 63, 65])
+@pytest.mark.parametrize("M,N", [(68, 132), (300, 1028)])
+def test_wgrad_ragged_k(device, M, N, K):
+    """dy.t() @ x takes any K: the row-contiguous reads clamp to k = K - 1 and are zeroed past it."""
+    _run("wgrad", M, N, K, device)
+
+
+@pytest.mark.parametrize("form,M,N,K", [("fwd", 68, 132, 60), ("wgrad", 68, 132, 63), ("mixed", 300, 1028, 260)])
+def test_strided_a(device, form, M, N, K):
+    _run(form, M, N, K, device, tag=4, strided_a=True)
+
+
+def test_k_zero_many_tiles(device):
+    M, N = 516, 512
+    g = _gen(M, N)
+    a, b = torch.empty(M, 0, device=device), torch.empty(0, N, device=device)
+    bias = torch.randn(N, generator=g).to(device)
+    cin = torch.randn(M, N, generator=g).to(device)
+    fn = _native.gemm_bf16
+    assert torch.equal(gemm_checks.run_checked(fn, a, b, round_operands=True), torch.zeros(M, N, device=device))
+    assert torch.equal(gemm_checks.run_checked(fn, a, b, cin=cin, bias=bias, round_operands=True), cin + bias)
+    assert torch.equal(gemm_checks.run_checked(fn, a, b, cin=cin, alias=True, round_operands=True), cin)
+
+
+@pytest.mark.parametrize("form", ["fwd", "wgrad"])
+def test_nan_isolation(device, form):
+    M, N, K = 300, 1028, 260
+    g = _gen(M, N, K, 9)
+    a, b = gemm_checks.operands(form, M, N, K, g, device)
+    gemm_checks.check_nan_isolation(_native.gemm_bf16, a, b, round_operands=True)

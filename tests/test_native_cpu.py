@@ -207,6 +207,36 @@ def test_binding_arity_matches_header():
     assert not bad, bad
 
 
+def test_gemm_smallm_ok_matches_documented_rule():
+    """gasfm_gemm_f32_smallm_ok against the rule at the top of csrc/gemm_smallm.hip, restated."""
+    def rule(mode, M, N, K):
+        if M < 0 or N < 1 or K < 1:
+            return 0
+        if mode in (0, 1):  # 8 K-slices of 16-wide steps; 1, 2, 4, 8 or 16 steps per wave
+            return int(K % 128 == 0 and K // 128 in (1, 2, 4, 8, 16) and N % 32 == 0)
+        if mode == 2:  # (I, J) = (M, N)
+            return int(M % 16 == 0 and N % 128 == 0 and K <= 256)
+        return 0
+    ok = _native.lib().gasfm_gemm_f32_smallm_ok
+    bad = [(mode, M, N, K)
+           for mode in range(4) for M in (-1, 0, 1, 16, 17) for N in (0, 31, 32, 96, 128, 160)
+           for K in (0, 1, 16, 127, 128, 192, 256, 257, 2048, 4096) if ok(mode, M, N, K) != rule(mode, M, N, K)]
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("name", ["gasfm_gemm_f32", "gasfm_gemm_bf16"])
+def test_gemm_empty_and_negative_shapes_return_before_any_launch(name):
+    """M = 0 or N = 0 is GASFM_OK with null pointers, a negative dimension the invalid-argument
+    status: both returns come before the first HIP call, so they need no device."""
+    fn = getattr(_native.lib(), name)
+    call = lambda M, N, K: fn(M, N, K, None, K, 1, None, N, 1, None, 0, None, None, N, None)
+    for M, N, K in ((0, 8, 8), (8, 0, 8), (0, 0, 0), (0, 8, 0)):
+        assert call(M, N, K) == _native.GASFM_OK, (M, N, K)
+    for M, N, K in ((-1, 8, 8), (8, -1, 8), (8, 8, -1)):
+        assert call(M, N, K) == _native.GASFM_ERR_INVALID, (M, N, K)
+        assert name.encode() in _native.lib().gasfm_last_error()
+
+
 def test_param_list_cache_follows_the_module_tree():
     """GraphAttnSfMNet._param_list (the forward's deferred-gradient check) is a cached list: it must
     follow a parameter replaced deep in the tree and a dtype / device conversion that creates new
