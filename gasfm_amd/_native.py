@@ -50,8 +50,6 @@ _SIGS = {
                                        _vp, _f32, _vp, _vp]),
     "gasfm_edge_epilogue_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _f32, _vp, _vp, _vp,
                                        _vp, _vp]),
-    "gasfm_edge_cam_bwd_part_rows": (_i32, [_i32]),
-    "gasfm_edge_cam_bwd_part_cols": (_i32, []),
     "gasfm_edge_seam_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _f32, _vp, _vp,
                                    _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _i32,
                                    _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
@@ -68,8 +66,6 @@ _SIGS = {
                                       _vp, _vp, _i64, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "gasfm_edge_cam_fwd": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _f32,
                                   _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
-    "gasfm_edge_cam_bwd": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp, _vp, _i64,
-                                  _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "gasfm_edge_prologue_bwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _f32, _vp,
                                        _vp, _vp, _i64, _vp]),
     "gasfm_segment_rowsum": (_i32, [_vp, _i32, _vp, _vp, _i64, _f32, _vp, _vp, _vp]),
@@ -176,8 +172,6 @@ _SIGS = {
     "gasfm_point_hub_fwd": (_i32, [_vp, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp]),
     "gasfm_point_tail_hub_fwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _f32] + [_vp] * 15),
-    "gasfm_point_hub_bwd_c": (_i32, [_vp, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_point_hub_bwd_ab": (_i32, [_vp, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gasfm_point_hub_bwd": (_i32, [_vp, _i64, _f32] + [_vp] * 17),
     "gasfm_point_head_part_shape": (_i32, [_i64, _i32, _vp]),
     "gasfm_point_head_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -622,23 +616,6 @@ def edge_cam_fwd(P, ln_w, ln_b, eps, Wpt, bpt, Wc, bc, XLp, pos, XR, att, bias, 
     check(st, "gasfm_edge_cam_fwd")
 
 
-def edge_cam_bwd_part_shape(n_items):
-    L = lib()
-    return int(L.gasfm_edge_cam_bwd_part_rows(n_items)), int(L.gasfm_edge_cam_bwd_part_cols())
-
-
-def edge_cam_bwd(P, ln_w, ln_b, eps, Wc, bc, XR, att, bias, slope, out, seg_max, seg_sum, gout, plan_items, n_items,
-                 dXLc, dXR, part_dxr, part, ldStat=4):
-    """Camera-attention backward with XLc recomputed from P: dXLc [E, 32], dXR, [datt | dbias] partials."""
-    _req(P, "P", 32)
-    ldXR = _rows32(XR, "XR")
-    st = lib().gasfm_edge_cam_bwd(_p(P), _p(ln_w), _p(ln_b), eps, _p(Wc), _p(bc), _p(XR), ldXR, _p(att), _p(bias),
-                                  slope, _p(out), out.stride(0), _p(seg_max), _p(seg_sum), ldStat, _p(gout),
-                                  gout.stride(0), _p(plan_items), n_items, _p(dXLc), dXLc.stride(0), _p(dXR),
-                                  dXR.stride(0), _p(part_dxr), _p(part), _stream(P))
-    check(st, "gasfm_edge_cam_bwd")
-
-
 def _ld_stat(seg_max):
     """row stride of the [N, heads] statistics (4 for their own tensors; the partial-row stride when
     they are columns of a packed partial buffer)"""
@@ -867,27 +844,6 @@ def point_tail_hub_fwd(prev, agg, Wp, bp, ln_w, ln_b, eps, Wm, bm, out, eps_h, g
                                         _p(Wm), _p(bm), _p(out), eps_h, _p(gA), _p(bA), _p(WA), _p(SA), _p(WB), _p(bB),
                                         _p(XL), _p(gC), _p(bC), _p(WC), _p(bWC), _p(WD), _p(bD), _p(XR), _stream(agg))
     check(st, "gasfm_point_tail_hub_fwd")
-
-
-def point_hub_bwd_c(X, eps, gC, bC, WC, bWC, WD, dXR, dRes, dX, part):
-    _req(X, "X", 64)
-    _req(dXR, "dXR", 32)
-    if dRes is not None:
-        _req(dRes, "dRes", 64)
-    st = lib().gasfm_point_hub_bwd_c(_p(X), X.shape[0], eps, _p(gC), _p(bC), _p(WC), _p(bWC), _p(WD), _p(dXR),
-                                     _p(dRes), _p(dX), _p(part), _stream(X))
-    check(st, "gasfm_point_hub_bwd_c")
-
-
-def point_hub_bwd_ab(X, eps, gA, bA, WA, WB, dSA, dXL, dRes, dX, part):
-    _req(X, "X", 64)
-    _req(dSA, "dSA", 32)
-    _req(dXL, "dXL", 64)
-    if dRes is not None:
-        _req(dRes, "dRes", 64)
-    st = lib().gasfm_point_hub_bwd_ab(_p(X), X.shape[0], eps, _p(gA), _p(bA), _p(WA), _p(WB), _p(dSA), _p(dXL),
-                                      _p(dRes), _p(dX), _p(part), _stream(X))
-    check(st, "gasfm_point_hub_bwd_ab")
 
 
 def point_hub_bwd(X, eps, gA, bA, WA, WB, gC, bC, WC, bWC, WD, dSA, dXL, dXR, dRes, dX, part_a, part_c):

@@ -1,5 +1,5 @@
-// Edge prologue with the CAMERA-direction GATv2 attention fused in, and the camera attention's
-// backward recomputing its source rows, gfx950.
+// Edge prologue with the CAMERA-direction GATv2 attention fused in, and its backward (the camera
+// attention's and the prologue's in one pass, recomputing the attention's source rows), gfx950.
 //
 // A block's edge prologue computes both convs' lin_l on P_hat = relu(LN(P)) (layers.py:232-234;
 // PyG's lin_l) -- XL = [XLp | XLc], 32 + 32 features per edge -- and the camera direction's
@@ -9,15 +9,15 @@
 //   edge_cam_fwd   over the camera plan's work items (one camera, <= max_piece edges each):
 //                  XLp is written (in point-segment order through pos, as edge_prologue_fwd does)
 //                  and XLc is consumed by an online softmax in registers -- never stored.
-//   edge_cam_bwd   the camera attention's backward (gat_attn.hip attn_bwd_*): XLc recomputed from
-//                  P (LayerNorm + 16 MFMAs per tile) instead of read back, dXLc written for
-//                  gasfm_edge_prologue_bwd (which takes the two halves of dXL separately), dXR per
-//                  camera, d att / d bias per workgroup.
+//   edge_cam_pbwd  the camera attention's backward (gat_attn.hip attn_bwd_*) with XLc recomputed
+//                  from P (LayerNorm + 16 MFMAs per tile) instead of read back, and the prologue's
+//                  backward on dXLc in registers: dP, dXR per camera, the weight / LayerNorm /
+//                  d att gradients per workgroup (see the section's own header).
 // HBM per edge and block: the forward writes 256 B less (XLc) and the camera attention's forward
 // read of XLc (128 B) is gone; the backward reads P (128 B) where it read XLc (128 B).
 //
-// MFMA orientation: the TRANSPOSED products XL^T = W P_hat^T (A = W from LDS, B = P_hat^T from the
-// wave's LDS tile) leave lane (g = l >> 4, c = l & 15) holding features 16 ot + 4 g + r (r < 4) of
+// MFMA orientation: the TRANSPOSED products XL^T = W P_hat^T (A = W slabs from LDS, B = P_hat^T
+// in registers, edge_cam_common.hpp) leave lane (g = l >> 4, c = l & 15) holding features 16 ot + 4 g + r (r < 4) of
 // EDGE c: one edge per lane column.  A head (8 features) is then 4 of the lane's registers plus
 // the same 4 of lane l ^ 16, the per-edge softmax state is one per lane and head, and a lane's
 // XLp / dXLc features are one float4 store per 16-feature tile (a row is 8 lanes x 16 B).
@@ -25,7 +25,7 @@
 // Semantics are those of gasfm_gat_attn_fwd / _bwd on the camera plan: complete items write
 // out[seg] (finalized with bias, or the raw acc), split items packed partial rows [acc 32 | max 4 |
 // sum 4] for gasfm_gat_attn_combine; empty segments give out = bias, max = -inf, sum = 0; d bias
-// sums gout over every segment (once, at its first item).
+// (the column sum of gout over every segment) is left to the host.
 #include "edge_cam_common.hpp"
 
 namespace gasfm {
@@ -45,24 +45,13 @@ __global__ __launch_bounds__(kThreads, GASFM_CAM_MINW) void edge_cam_fwd_kernel(
     float slope, const gasfm_work_item* __restrict__ items, int n_items, int finalize, float* __restrict__ out,
     int64_t ldOut, float* __restrict__ seg_max, float* __restrict__ seg_sum, int64_t ldStat,
     float* __restrict__ part) {
-  __shared__ __attribute__((aligned(16))) float Wl[kCamR ? NX * F : NX * LDA];  // slabs, or Wl[n][k] = [Wpt; Wc][n][k]
-  __shared__ float tiles[kCamR ? 1 : kWaves][TR * LD34];
-  if (kCamR) {
-    stage_slabs32<NX, kThreads>([&](int q) { return q < F * F ? Wpt[q] : Wc[q - F * F]; }, Wl);
-  } else {
-    Stage<NX * F, kThreads> sw;
-    sw.load([&](int q) { return q < F * F ? Wpt[q] : Wc[q - F * F]; });
-    sw.store([&](int q, float v) { Wl[(q / F) * LDA + q % F] = v; });
-  }
+  __shared__ __attribute__((aligned(16))) float Wl[NX * F];  // [Wpt; Wc] slabs
+  stage_slabs32<NX, kThreads>([&](int q) { return q < F * F ? Wpt[q] : Wc[q - F * F]; }, Wl);
   __syncthreads();
   const int lane = threadIdx.x & (kW - 1), wave = threadIdx.x / kW;
   const int c = lane & 15, g = lane >> 4;
-  float* T = tiles[kCamR ? 0 : wave];
-  float4 g4 = make_float4(1.f, 1.f, 1.f, 1.f), b4 = make_float4(0.f, 0.f, 0.f, 0.f);
   float g8[2][4], b8[2][4];  // gamma / beta at the slab features 16 u + 4 g + j
   if (LN) {
-    g4 = *reinterpret_cast<const float4*>(gam + (lane & 7) * 4);
-    b4 = *reinterpret_cast<const float4*>(bet + (lane & 7) * 4);
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -86,17 +75,13 @@ __global__ __launch_bounds__(kThreads, GASFM_CAM_MINW) void edge_cam_fwd_kernel(
     }
   const int gw = blockIdx.x * kWaves + wave, nw = gridDim.x * kWaves;
 
-  float4 np[2];
   f32x4 ns[2];
   int32_t npos = 0;  // point-order row of this lane's edge (column c)
   // branch-free: without pos the index load reads P's first words and is not used (a load under a
   // branch makes the join wait for every load in flight)
   const int32_t* posp = pos ? pos : reinterpret_cast<const int32_t*>(P);
   auto issue = [&](int64_t row0, int nrows) {
-    if (kCamR)
-      load_slabs32(P, row0, nrows, ns, lane);
-    else
-      load_rows(P, F, row0, nrows, np, lane);
+    load_slabs32(P, row0, nrows, ns, lane);
     npos = posp[row0 + (c < nrows ? c : 0)];
   };
   auto rows_at = [](const gasfm_work_item& w, int64_t row0) { return int(w.end - row0 < TR ? w.end - row0 : TR); };
@@ -123,7 +108,6 @@ __global__ __launch_bounds__(kThreads, GASFM_CAM_MINW) void edge_cam_fwd_kernel(
     for (int64_t row0 = w.begin; row0 < w.end; row0 += TR) {
       const int nrows = rows_at(w, row0);
       f32x4 ph[2] = {ns[0], ns[1]};
-      if (!kCamR) phat_to_lds<LN>(np, nrows, g4, b4, eps, T, lane);
       const int64_t dst = pos ? int64_t(npos) : row0 + (c < nrows ? c : 0);
       {  // the next tile (this item's, else the next item's first; the last one re-reads itself)
         int64_t r1 = row0;
@@ -138,13 +122,8 @@ __global__ __launch_bounds__(kThreads, GASFM_CAM_MINW) void edge_cam_fwd_kernel(
         issue(r1, n1);
       }
       f32x4 acc[4] = {zero4(), zero4(), zero4(), zero4()};
-      if (kCamR) {
-        phat_slabs<LN>(ph, g8, b8, eps);
-        xl_slabs<4>(reinterpret_cast<const float4*>(Wl), ph, acc, lane);
-      } else {
-        wave_sync();
-        xl_t<4>(Wl, T, acc, c, g);
-      }
+      phat_slabs<LN>(ph, g8, b8, eps);
+      xl_slabs<4>(reinterpret_cast<const float4*>(Wl), ph, acc, lane);
       const bool valid = c < nrows;
       // point half: this lane's 2 x 4 features of edge c (non-temporal: streamed once by the point
       // attention)
@@ -175,7 +154,6 @@ __global__ __launch_bounds__(kThreads, GASFM_CAM_MINW) void edge_cam_fwd_kernel(
           m[q] = mn;
         }
       }
-      if (!kCamR) wave_sync();  // T is rewritten by the next tile
     }
     // merge the 16 edge columns' states
 #pragma unroll
@@ -216,193 +194,6 @@ __global__ __launch_bounds__(kThreads, GASFM_CAM_MINW) void edge_cam_fwd_kernel(
 }
 
 // =============================================================================================
-// backward of the camera attention, XLc recomputed from P
-// =============================================================================================
-// per workgroup partial row: [32 datt | 32 dbias]
-constexpr int BP_PART = 2 * F;
-
-template <bool LN>
-__global__ __launch_bounds__(kThreads, GASFM_CAM_MINW) void edge_cam_bwd_kernel(
-    const float* __restrict__ P, const float* __restrict__ gam, const float* __restrict__ bet, float eps,
-    const float* __restrict__ Wc, const float* __restrict__ bc, const float* __restrict__ XR, int64_t ldXR,
-    const float* __restrict__ att, const float* __restrict__ bias, float slope, const float* __restrict__ out,
-    int64_t ldOut, const float* __restrict__ seg_max, const float* __restrict__ seg_sum, int64_t ldStat,
-    const float* __restrict__ gout, int64_t ldG, const gasfm_work_item* __restrict__ items, int n_items,
-    float* __restrict__ dXLc, int64_t ldD, float* __restrict__ dXR, int64_t ldDXR, float* __restrict__ part_dxr,
-    float* __restrict__ part) {
-  __shared__ __attribute__((aligned(16))) float Wl[kCamR ? F * F : F * LDA];  // slabs, or Wl[n][k] = Wc[n][k]
-  __shared__ float tiles[kWaves][TR * LD34];  // (also the final reduction's scratch)
-  if (kCamR) {
-    stage_slabs32<F, kThreads>([&](int q) { return Wc[q]; }, Wl);
-  } else {
-    Stage<F * F, kThreads> sw;
-    sw.load([&](int q) { return Wc[q]; });
-    sw.store([&](int q, float v) { Wl[(q / F) * LDA + q % F] = v; });
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & (kW - 1), wave = threadIdx.x / kW;
-  const int c = lane & 15, g = lane >> 4;
-  float* T = tiles[wave];
-  float4 g4 = make_float4(1.f, 1.f, 1.f, 1.f), b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float g8[2][4], b8[2][4];  // gamma / beta at the slab features 16 u + 4 g + j
-  if (LN) {
-    g4 = *reinterpret_cast<const float4*>(gam + (lane & 7) * 4);
-    b4 = *reinterpret_cast<const float4*>(bet + (lane & 7) * 4);
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        g8[u][j] = gam[16 * u + 4 * g + j];
-        b8[u][j] = bet[16 * u + 4 * g + j];
-      }
-  }
-  float bcv[2][4], attv[2][4], biasv[2][4], datt[2][4], dbias[2][4];
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int f = 16 * q + 4 * g + r;
-      bcv[q][r] = bc[f];
-      attv[q][r] = att[f];
-      biasv[q][r] = bias[f];
-      datt[q][r] = dbias[q][r] = 0.f;
-    }
-  const int gw = blockIdx.x * kWaves + wave, nw = gridDim.x * kWaves;
-
-  float4 np[2];
-  f32x4 ns[2];
-  auto issue = [&](int64_t row0, int nrows) {
-    if (kCamR)
-      load_slabs32(P, row0, nrows, ns, lane);
-    else
-      load_rows(P, F, row0, nrows, np, lane);
-  };
-  auto rows_at = [](const gasfm_work_item& w, int64_t row0) { return int(w.end - row0 < TR ? w.end - row0 : TR); };
-  gasfm_work_item w{0, 0, 0, -1};
-  if (gw < n_items) {
-    w = items[gw];
-    if (w.begin < w.end) issue(w.begin, rows_at(w, w.begin));
-  }
-  for (int it = gw; it < n_items; it += nw) {
-    const int64_t seg = w.seg;
-    // per-camera constants: XR, gout, out - bias at this lane's features; per head the forward's
-    // max, 1 / (sum + 1e-16) and delta = sum_j alpha_j (g . XL_j) = g . (out - bias)
-    float xr[2][4], gv[2][4], M[2], inv[2], delta[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int f0 = 16 * q + 4 * g, h = 2 * q + (g >> 1);
-      const float4 x4 = *reinterpret_cast<const float4*>(XR + seg * ldXR + f0);
-      const float4 g4v = *reinterpret_cast<const float4*>(gout + seg * ldG + f0);
-      const float4 o4 = *reinterpret_cast<const float4*>(out + seg * ldOut + f0);
-      xr[q][0] = x4.x, xr[q][1] = x4.y, xr[q][2] = x4.z, xr[q][3] = x4.w;
-      gv[q][0] = g4v.x, gv[q][1] = g4v.y, gv[q][2] = g4v.z, gv[q][3] = g4v.w;
-      const float o[4] = {o4.x, o4.y, o4.z, o4.w};
-      float d = 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) d = fmaf(gv[q][r], o[r] - biasv[q][r], d);
-      delta[q] = xsum16(d);
-      M[q] = seg_max[seg * ldStat + h];
-      inv[q] = 1.f / (seg_sum[seg * ldStat + h] + 1e-16f);
-    }
-    const bool first = it == 0 || items[it - 1].seg != w.seg;
-    if (first && c == 0) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dbias[q][r] += gv[q][r];
-    }
-    float dxr[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    gasfm_work_item wn{0, 0, 0, -1};
-    const bool more = it + nw < n_items;
-    if (more) wn = items[it + nw];
-    if (w.begin >= w.end && more && wn.begin < wn.end) issue(wn.begin, rows_at(wn, wn.begin));
-    for (int64_t row0 = w.begin; row0 < w.end; row0 += TR) {
-      const int nrows = rows_at(w, row0);
-      f32x4 ph[2] = {ns[0], ns[1]};
-      if (!kCamR) phat_to_lds<LN>(np, nrows, g4, b4, eps, T, lane);
-      {  // the next tile (see edge_cam_fwd_kernel)
-        int64_t r1 = row0;
-        int n1 = nrows;
-        if (row0 + TR < w.end) {
-          r1 = row0 + TR;
-          n1 = rows_at(w, r1);
-        } else if (more && wn.begin < wn.end) {
-          r1 = wn.begin;
-          n1 = rows_at(wn, r1);
-        }
-        issue(r1, n1);
-      }
-      f32x4 xc[2] = {zero4(), zero4()};
-      if (kCamR) {
-        phat_slabs<LN>(ph, g8, b8, eps);
-        xl_slabs<2>(reinterpret_cast<const float4*>(Wl), ph, xc, lane);
-      } else {
-        wave_sync();
-        xl_t<2>(Wl, T, xc, c, g);
-      }
-      const bool valid = c < nrows;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        float xl[4], z[4], lz[4], p = 0.f, da = 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          xl[r] = xc[q][r] + bcv[q][r];
-          z[r] = xl[r] + xr[q][r];
-          lz[r] = leaky(z[r], slope);
-          p = fmaf(lz[r], attv[q][r], p);
-          da = fmaf(gv[q][r], xl[r], da);
-        }
-        p = xsum16(p);
-        da = xsum16(da);
-        const float alpha = valid ? __expf(p - M[q]) * inv[q] : 0.f;
-        const float de = alpha * (da - delta[q]);
-        float dx[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float dz = de * attv[q][r] * (z[r] > 0.f ? 1.f : slope);
-          dx[r] = fmaf(alpha, gv[q][r], dz);
-          dxr[q][r] += dz;
-          datt[q][r] = fmaf(de, lz[r], datt[q][r]);
-        }
-        if (valid)
-          *reinterpret_cast<float4*>(dXLc + (row0 + c) * ldD + 16 * q + 4 * g) = make_float4(dx[0], dx[1], dx[2], dx[3]);
-      }
-      if (!kCamR) wave_sync();  // T is rewritten by the next tile
-    }
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      float v[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = group_sum<16>(dxr[q][r]);
-      if (c == 0) {
-        float* d = (w.slot < 0) ? dXR + seg * ldDXR : part_dxr + int64_t(w.slot) * F;
-        *reinterpret_cast<float4*>(d + 16 * q + 4 * g) = make_float4(v[0], v[1], v[2], v[3]);
-      }
-    }
-    w = wn;
-  }
-  // d att / d bias: sum over the 16 edge columns, then over the workgroup's waves (ordered)
-  float v[16];
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      v[q * 4 + r] = group_sum<16>(datt[q][r]);
-      v[8 + q * 4 + r] = group_sum<16>(dbias[q][r]);
-    }
-  wg_reduce_ordered<16, kWaves, kWaves * TR * LD34>(v, &tiles[0][0], wave, lane);
-  if (wave == 0 && c == 0) {
-    float* o = part + int64_t(blockIdx.x) * BP_PART;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      *reinterpret_cast<float4*>(o + 16 * q + 4 * g) = make_float4(v[q * 4], v[q * 4 + 1], v[q * 4 + 2], v[q * 4 + 3]);
-      *reinterpret_cast<float4*>(o + F + 16 * q + 4 * g) =
-          make_float4(v[8 + q * 4], v[8 + q * 4 + 1], v[8 + q * 4 + 2], v[8 + q * 4 + 3]);
-    }
-  }
-}
-
-// =============================================================================================
 // backward, fused: camera attention + edge prologue of the block in ONE pass over the camera
 // plan's items (gasfm_edge_cam_pbwd).  Per 16-edge tile, all in the T layout (lane (g, c): edge c,
 // features 16 u + 4 g + j) except the weight-gradient operands:
@@ -410,8 +201,8 @@ __global__ __launch_bounds__(kThreads, GASFM_CAM_MINW) void edge_cam_bwd_kernel(
 //   dP_hat = dXLp Wpt + dXLc Wc + dRes (scale Wp[:, :32])  (transposed products: B = T-layout rows);
 //   dP = LN_bwd(mask * dP_hat) + dRes (stored), dgamma, dbeta;
 //   dW += [dXLp | dXLc]^T P_hat, db  (C-layout operands through a per-wave LDS transpose).
-// Replaces edge_cam_bwd + edge_prologue_bwd: dXLc (128 B per edge) is neither written nor read
-// back, and P is read once.  Partial rows per workgroup: [dW 64x32 | db 64 | dgamma 32 | dbeta 32 |
+// dXLc (128 B per edge) is neither written nor read back, and P is read once (a separate camera
+// attention backward followed by edge_prologue_bwd did both: 224 + 522 us at config 4).  Partial rows per workgroup: [dW 64x32 | db 64 | dgamma 32 | dbeta 32 |
 // datt 32 | 0 (32: the bias gradient is the host's column sum of gout)].
 // =============================================================================================
 // Measured choices (tools/edge_bench.py, tools/gpu_ab_libs.sh): round 5's T-layout
@@ -422,6 +213,7 @@ __global__ __launch_bounds__(kThreads, GASFM_CAM_MINW) void edge_cam_bwd_kernel(
 // tiles, dXLp in point order, block 0's epilogue folded in, XLc kept by the forward seam, static
 // wave priority.
 constexpr int PB2_PRO = NX * F + NX + 2 * F;  // the prologue_bwd part row
+constexpr int BP_PART = 2 * F;                // [32 datt | 32 zeros]
 constexpr int PB2_PART = PB2_PRO + BP_PART;
 constexpr int LDT = F + 4;                    // transpose tile row stride
 constexpr int PB_NDW = 20;                    // (DWP) per-lane dWp sums: 16 MFMA values + 4 P0 terms
@@ -593,7 +385,8 @@ __global__ __launch_bounds__(kThreads, GASFM_PBWD_MINW) void edge_cam_pbwd_kerne
     const auto dPrs = rows_rsrc(dP, F, ibeg, ilen);
     // (EPI) dP0 rows of this item; without dP0 an empty range (every store dropped)
     const auto dP0rs = (EPI && ep.dP0) ? rows_rsrc(ep.dP0, 2, ibeg, ilen) : rows_rsrc(dP, F, ibeg, 0);
-    // per-camera constants of the attention backward (edge_cam_bwd_kernel)
+    // per-camera constants of the attention backward: XR, gout at this lane's features; per head the
+    // forward's max, 1 / (sum + 1e-16) and delta = sum_j alpha_j (g . XL_j) = g . (out - bias)
     f32x4 xr[2], gv[2];
     float M[2], inv[2], delta[2];
 #pragma unroll
@@ -927,17 +720,10 @@ int grid_cam_pbwd(int n_items) {
                        n_items, kWaves);
 }
 
-int grid_cam_bwd(int n_items) {
-  return resident_grid(reinterpret_cast<const void*>(&edge_cam_bwd_kernel<true>), kThreads, 0, n_items, kWaves);
-}
-
 }  // namespace
 }  // namespace gasfm
 
 using namespace gasfm;
-
-extern "C" int32_t gasfm_edge_cam_bwd_part_rows(int32_t n_items) { return grid_cam_bwd(n_items > 0 ? n_items : 1); }
-extern "C" int32_t gasfm_edge_cam_bwd_part_cols(void) { return BP_PART; }
 
 extern "C" int gasfm_edge_cam_fwd(const float* P, const float* ln_w, const float* ln_b, float eps, const float* Wpt,
                                   const float* bpt, const float* Wc, const float* bc, float* XLp, int64_t ldXLp,
@@ -966,35 +752,6 @@ extern "C" int gasfm_edge_cam_fwd(const float* P, const float* ln_w, const float
   else
     launch(&edge_cam_fwd_kernel<false>);
   return launch_status("gasfm_edge_cam_fwd");
-}
-
-extern "C" int gasfm_edge_cam_bwd(const float* P, const float* ln_w, const float* ln_b, float eps, const float* Wc,
-                                  const float* bc, const float* XR, int64_t ldXR, const float* att, const float* bias,
-                                  float slope, const float* out, int64_t ldOut, const float* seg_max,
-                                  const float* seg_sum, int64_t ldStat, const float* gout, int64_t ldG,
-                                  const gasfm_work_item* items, int32_t n_items, float* dXLc, int64_t ldD, float* dXR,
-                                  int64_t ldDXR, float* part_dxr, float* part, void* stream) {
-  GASFM_REQUIRE(n_items >= 0 && P && Wc && bc && XR && att && bias && out && seg_max && seg_sum && gout && items &&
-                    dXLc && dXR && part,
-                "gasfm_edge_cam_bwd: null pointer");
-  GASFM_REQUIRE(ldXR % 4 == 0 && ldOut % 4 == 0 && ldG % 4 == 0 && ldD % 4 == 0 && ldDXR % 4 == 0 && aligned16(P) &&
-                    aligned16(XR) && aligned16(out) && aligned16(gout) && aligned16(dXLc) && aligned16(dXR) &&
-                    (!part_dxr || aligned16(part_dxr)) && (!ln_w || (aligned16(ln_w) && aligned16(ln_b))),
-                "gasfm_edge_cam_bwd: 16-byte rows required");
-  GASFM_REQUIRE(slope >= 0.f && slope <= 1.f, "gasfm_edge_cam_bwd: negative_slope %g outside [0, 1]", double(slope));
-  if (n_items == 0) return GASFM_OK;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int grid = grid_cam_bwd(n_items);
-  auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), 0, st, P, ln_w, ln_b, eps, Wc, bc, XR, ldXR, att, bias, slope,
-                       out, ldOut, seg_max, seg_sum, ldStat, gout, ldG, items, n_items, dXLc, ldD, dXR, ldDXR,
-                       part_dxr, part);
-  };
-  if (ln_w)
-    launch(&edge_cam_bwd_kernel<true>);
-  else
-    launch(&edge_cam_bwd_kernel<false>);
-  return launch_status("gasfm_edge_cam_bwd");
 }
 
 extern "C" int32_t gasfm_edge_cam_pbwd_part_rows(int32_t n_items) { return grid_cam_pbwd(n_items > 0 ? n_items : 1); }

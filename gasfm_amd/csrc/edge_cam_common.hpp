@@ -16,8 +16,6 @@ using namespace tile;
 constexpr int F = 32;       // projection features (n_feat_proj) = HC of both convs (H = 4, C = 8)
 constexpr int H = 4;
 constexpr int NX = 64;      // [point | camera] lin_l outputs
-constexpr int LD34 = 34;    // LDS row stride of the P_hat tile
-constexpr int LDA = 36;     // LDS row stride of staged weights W[out][in] (A operand, 2-way banks)
 constexpr int PART = F + 2 * H;  // packed partial row
 
 // leaky_relu for 0 <= slope <= 1 (the launchers require it; GATv2's 0.2): max(z, slope z) is
@@ -39,75 +37,17 @@ __device__ __forceinline__ gasfm_work_item uniform_item(const gasfm_work_item& w
                          __builtin_amdgcn_readfirstlane(w.end), __builtin_amdgcn_readfirstlane(w.slot)};
 }
 
-// Rows of a 16 x 32 tile in row layout: lane l holds row (l >> 3) + 8u (u = 0, 1), columns
-// 4 (l & 7) .. + 3.  Rows >= nrows re-read row 0 (always valid); phat_to_lds writes zeros for
-// them.  No select on the loaded registers here: these loads are the next tile's prefetch, and
-// a select right after them would make the wave wait for them at once.
-__device__ __forceinline__ void load_rows(const float* __restrict__ X, int64_t ld, int64_t row0, int nrows,
-                                          float4 (&v)[2], int lane) {
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int r = (lane >> 3) + 8 * u;
-    v[u] = *reinterpret_cast<const float4*>(X + (row0 + (r < nrows ? r : 0)) * ld + (lane & 7) * 4);
-  }
-}
-
-// relu(LN(P)) of the row-layout registers into the wave's LDS tile (row stride 34); rows >= nrows
-// are zeros.  LN == false: the raw rows (the final update, graph_attn_sfm.py:141-148).
-template <bool LN>
-__device__ __forceinline__ void phat_to_lds(const float4 (&v)[2], int nrows, float4 g4, float4 b4, float eps,
-                                            float* T, int lane) {
-  const int cc = (lane & 7) * 4;
-  const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int r = (lane >> 3) + 8 * u;
-    const float x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-    float mean = 0.f, rstd = 1.f;
-    if (LN) {
-      mean = group_sum<8>(x[0] + x[1] + x[2] + x[3]) * (1.f / F);
-      float q = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) q = fmaf(x[k] - mean, x[k] - mean, q);
-      rstd = rsq_normal(group_sum<8>(q) * (1.f / F) + eps);
-    }
-    float ph[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float xh = LN ? (x[k] - mean) * rstd : x[k];
-      ph[k] = (r < nrows) ? (LN ? fmaxf(fmaf(xh, gg[k], bb[k]), 0.f) : xh) : 0.f;
-    }
-    float2* d = reinterpret_cast<float2*>(T + r * LD34 + cc);
-    d[0] = make_float2(ph[0], ph[1]);
-    d[1] = make_float2(ph[2], ph[3]);
-  }
-}
-
-// acc[ot] += W[16 ot + c][k] P_hat[edge c][k] over k < 32: A = W rows (LDS, stride LDA), B = P_hat^T
-template <int OT>
-__device__ __forceinline__ void xl_t(const float* Wl, const float* T, f32x4 (&acc)[OT], int c, int g) {
-#pragma unroll
-  for (int s = 0; s < F / 4; ++s) {
-    const float b = T[c * LD34 + 4 * s + g];
-#pragma unroll
-    for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma16(Wl[(16 * ot + c) * LDA + 4 * s + g], b, acc[ot]);
-  }
-}
-
-// ---- register-resident front end (GASFM_EDGE_CAM_R, default): no P_hat tile in LDS.
+// ---- register-resident front end: no P_hat tile in LDS.
 // P rows are loaded straight into the B-operand layout of the transposed product ("slabs": lane
 // (g, c) holds P[edge c][16 u + 4 g + j], j < 4, u = 0, 1 -- the k index of MFMA step (u, j) is
 // 16 u + 4 g + j), the LayerNorm runs on those registers (a row's 32 features: 8 per lane, then
 // the 4 lane groups), and the weights are staged once per workgroup as float4 slabs in the same
-// k order (one ds_read_b128 per 4 MFMAs; was a ds_read_b32 per MFMA operand and a 16 x 34 LDS
-// tile write + read per 16 edges).  The accumulators come out exactly as xl_t's (lane (g, c):
-// features 16 ot + 4 g + r of edge c).
-#ifndef GASFM_EDGE_CAM_R
-#define GASFM_EDGE_CAM_R 1
-#endif
-constexpr bool kCamR = GASFM_EDGE_CAM_R != 0;
+// k order (one ds_read_b128 per 4 MFMAs).  The accumulators come out with lane (g, c) holding
+// features 16 ot + 4 g + r of edge c.  (An LDS-staged front end -- a ds_read_b32 per MFMA operand
+// and a 16 x 34 LDS tile write + read per 16 edges -- measured 268 vs 251-256 us; git history at
+// b512b46.)
 #ifndef GASFM_CAM_MINW
-#define GASFM_CAM_MINW 3  // minimum waves per SIMD (168 VGPRs): fwd 282 -> 251 us, bwd 270 -> 236 us vs 2 (tools/edge_bench.py)
+#define GASFM_CAM_MINW 3  // minimum waves per SIMD (168 VGPRs): edge_cam_fwd 282 -> 251 us vs 2 (tools/edge_bench.py)
 #endif
 
 // W [O x 32] rows (o < O) -> slabs Q[(ot * 2 + u) * 64 + 16 g + c] = (W[16 ot + c][16 u + 4 g + j], j < 4)

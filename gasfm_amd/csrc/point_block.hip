@@ -20,10 +20,20 @@
 // d agg in the same pass.
 //
 // Layout: wave = 16-row tile (tile.hpp); GEMMs on v_mfma_f32_16x16x4_f32 against weights
-// staged once per workgroup in LDS (row stride 80 for 64 columns, 48 for 32: == 16 mod 32,
-// conflict-free B reads).  LayerNorm statistics are recomputed from p in the backward pass.
-// Weight / bias / gamma / beta gradients leave as per-workgroup partial rows reduced by
-// gasfm_colsum in a fixed order (deterministic, no atomics).
+// staged once per workgroup in LDS as float4 slabs in the order the MFMA operands are read.  A
+// tile stays in registers from its global load to its global store: the forward kernels
+// (*_fwd_t_kernel) chain transposed products, the backward kernels (*_bwd_r_kernel) read every
+// tensor in the layout its consumer wants; see the comment at the head of each section.
+// LayerNorm statistics are recomputed from p in the backward pass.  Weight / bias / gamma /
+// beta gradients leave as per-workgroup partial rows reduced by gasfm_colsum in a fixed order
+// (deterministic, no atomics).
+//
+// History: the first generation of these kernels staged every tile through LDS (87-150 KB per
+// workgroup) and ran the hub backward as two passes with an extra write + read of dp.  The
+// register-resident forms measured 40.7 -> 35.4 us (tail forward), 57.2 -> 43.9 us (hub forward),
+// 93.6 -> 79.6 us (tail backward) and 63 + 78 -> 116 us (hub backward, n = 200k) and replaced
+// them (the kernel table; profiles/r6_ab_kernels_sched_ring.txt); the old kernels and
+// their build switches are in the git history at b512b46.
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
@@ -36,909 +46,19 @@ using namespace tile;
 
 constexpr int FP = 64;  // n_feat_scenepoint
 constexpr int FA = 32;  // n_feat_proj (aggregation / projection width)
-constexpr int L66 = 66, L34 = 34, L80 = 80, L48 = 48;
-// A/B knobs (tools/point_bench.py): next-tile register prefetch in the forward / backward
-// kernels, and waves per backward workgroup (8: 2 waves per SIMD at <= 256 VGPRs each; 4: one
-// wave per SIMD, room for the prefetch registers without spilling)
-#ifndef GASFM_PT_FWD_PREFETCH
-#define GASFM_PT_FWD_PREFETCH 1
-#endif
-#ifndef GASFM_PT_BWD_PREFETCH
-#define GASFM_PT_BWD_PREFETCH 0
-#endif
-#ifndef GASFM_PT_BWD_WAVES
-#define GASFM_PT_BWD_WAVES 8
-#endif
-constexpr bool kFwdPf = GASFM_PT_FWD_PREFETCH != 0, kBwdPf = GASFM_PT_BWD_PREFETCH != 0;
-constexpr int kWaves8 = GASFM_PT_BWD_WAVES, kThreads8 = kWaves8 * kW;
 
-// partial-row layouts (floats)
-constexpr int TAIL_PART = FP * FP + FP * FA + 4 * FP;                 // dWm dWp dbm dbp dgam dbet
-
-// per-row mean / rstd of a 64-wide tile in row layout (rows_load<64>: the 16 lanes of a lane
-// group hold one row) -> MS, RS
-__device__ __forceinline__ void row_stats64(const float4 (&v)[4], float eps, float* MS, float* RS, int lane) {
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int r = (lane >> 4) + 4 * u;
-    const float x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-    const float mean = sum16(x[0] + x[1] + x[2] + x[3]) * (1.f / FP);
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) q = fmaf(x[k] - mean, x[k] - mean, q);
-    const float rstd = rsq_normal(sum16(q) * (1.f / FP) + eps);
-    if ((lane & 15) == 0) {
-      MS[r] = mean;
-      RS[r] = rstd;
-    }
-  }
-}
-
-// LayerNorm + ReLU backward of one row held as 16 lanes x 4 column tiles (C layout):
-// returns dx, accumulates dgamma / dbeta.  dh: upstream gradient of relu(xh*g + b).
-__device__ __forceinline__ void ln_relu_bwd_row(const float (&xh)[4], const float (&dh)[4], const float (&g)[4],
-                                                const float (&b)[4], float rstd, float (&dg)[4], float (&db)[4],
-                                                float (&dx)[4]) {
-  float gv[4], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-    const float dy = fmaf(xh[nt], g[nt], b[nt]) > 0.f ? dh[nt] : 0.f;
-    dg[nt] = fmaf(dy, xh[nt], dg[nt]);
-    db[nt] += dy;
-    gv[nt] = dy * g[nt];
-    s1 += gv[nt];
-    s2 = fmaf(gv[nt], xh[nt], s2);
-  }
-  s1 = sum16(s1) * (1.f / FP);
-  s2 = sum16(s2) * (1.f / FP);
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) dx[nt] = rstd * (gv[nt] - s1 - xh[nt] * s2);
-}
-
-// Every kernel below: per 16-row tile, all global loads are issued first as coalesced float4
-// rows (tile.hpp rows_load), staged into the wave's LDS slice, consumed from LDS in the MFMA
-// A / B / C layouts, and the outputs leave through an LDS staging tile as float4 rows.
-
-// ----------------------------------------------------------------------------- tail
-template <bool PREV>
-__global__ __launch_bounds__(kThreads) void point_tail_fwd_kernel(
-    const float* __restrict__ prev, const float* __restrict__ agg, int64_t N, const float* __restrict__ Wp,
-    const float* __restrict__ bp, const float* __restrict__ gam, const float* __restrict__ bet, float eps,
-    const float* __restrict__ Wm, const float* __restrict__ bm, float* __restrict__ out) {
-  constexpr int PW = TR * L34 + 2 * TR * L66;  // Ag, Pv (prev, then the output), Ph
-  __shared__ float WpT[FA * L80];              // WpT[j][o] = Wp[o][j]
-  __shared__ float WmT[FP * L80];              // WmT[k][o] = Wm[o][k]
-  __shared__ float tiles[kWaves * PW];
-  {
-    Stage<FP * FA, kThreads> sp;
-    Stage<FP * FP, kThreads> sm;
-    sp.load([&](int q) { return Wp[q]; });
-    sm.load([&](int q) { return Wm[q]; });
-    sp.store([&](int q, float v) { WpT[(q % FA) * L80 + q / FA] = v; });
-    sm.store([&](int q, float v) { WmT[(q % FP) * L80 + q / FP] = v; });
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & (kW - 1), wave = threadIdx.x / kW;
-  const int c = lane & 15, g = lane >> 4;
-  float* Ag = tiles + wave * PW;
-  float* Pv = Ag + TR * L34;
-  float* Ph = Pv + TR * L66;
-  float bpv[4], bmv[4], gv[4], bv[4];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-    bpv[nt] = bp[nt * 16 + c];
-    bmv[nt] = bm[nt * 16 + c];
-    gv[nt] = gam[nt * 16 + c];
-    bv[nt] = bet[nt * 16 + c];
-  }
-  const int64_t ntiles = (N + TR - 1) / TR;
-  const int64_t gw = int64_t(blockIdx.x) * kWaves + wave, nw = int64_t(gridDim.x) * kWaves;
-  // next-tile register prefetch: tile t + nw's rows are requested right after tile t's are
-  // staged, so their latency overlaps this tile's MFMA work
-  float4 va[2], vp[4];
-  auto fetch = [&](int64_t tt) {
-    const int64_t r0 = tt * TR;
-    const int nr = int(N - r0 < TR ? N - r0 : TR);
-    rows_load<FA>(agg, FA, r0, nr, va, lane);
-    if (PREV) rows_load<FP>(prev, FP, r0, nr, vp, lane);
-  };
-  if (kFwdPf && gw < ntiles) fetch(gw);
-  for (int64_t t = gw; t < ntiles; t += nw) {
-    const int64_t row0 = t * TR;
-    const int nrows = int(N - row0 < TR ? N - row0 : TR);
-    if constexpr (!kFwdPf) fetch(t);
-    rows_to_lds<FA, L34>(Ag, va, lane);
-    if (PREV) rows_to_lds<FP, L66>(Pv, vp, lane);
-    if (kFwdPf && t + nw < ntiles) fetch(t + nw);
-    wave_sync();
-    f32x4 xa[4] = {zero4(), zero4(), zero4(), zero4()};
-#pragma unroll
-    for (int s = 0; s < FA / 4; ++s) {
-      const float a = Ag[c * L34 + 4 * s + g];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) xa[nt] = mfma16(a, WpT[(4 * s + g) * L80 + nt * 16 + c], xa[nt]);
-    }
-    float xv[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int e = 4 * g + r;
-      float s1 = 0.f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        xv[nt][r] = xa[nt][r] + bpv[nt] + (PREV ? Pv[e * L66 + nt * 16 + c] : 0.f);
-        s1 += xv[nt][r];
-      }
-      const float mean = sum16(s1) * (1.f / FP);
-      float q = 0.f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) q = fmaf(xv[nt][r] - mean, xv[nt][r] - mean, q);
-      const float rstd = rsq_normal(sum16(q) * (1.f / FP) + eps);
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-        Ph[e * L66 + nt * 16 + c] = fmaxf(fmaf((xv[nt][r] - mean) * rstd, gv[nt], bv[nt]), 0.f);
-    }
-    wave_sync();
-    f32x4 acc[4] = {zero4(), zero4(), zero4(), zero4()};
-#pragma unroll
-    for (int s = 0; s < FP / 4; ++s) {
-      const float a = Ph[c * L66 + 4 * s + g];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) acc[nt] = mfma16(a, WmT[(4 * s + g) * L80 + nt * 16 + c], acc[nt]);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) Pv[(4 * g + r) * L66 + nt * 16 + c] = xv[nt][r] + acc[nt][r] + bmv[nt];
-    wave_sync();
-    float4 vo[4];
-    rows_from_lds<FP, L66>(Pv, vo, lane);
-    rows_store<FP>(out, FP, row0, nrows, vo, lane);
-    wave_sync();
-  }
-}
-
-// dx = dout + LN_bwd(mask * (dout W_m)) (== d prev), dagg = dx W_p; partial row per workgroup
-// [dWm 64x64 | dWp 64x32 | dbm 64 | dbp 64 | dgam 64 | dbet 64]
-template <bool PREV>
-__global__ __launch_bounds__(kThreads8) void point_tail_bwd_kernel(
-    const float* __restrict__ dout, const float* __restrict__ prev, const float* __restrict__ agg, int64_t N,
-    const float* __restrict__ Wp, const float* __restrict__ bp, const float* __restrict__ gam,
-    const float* __restrict__ bet, float eps, const float* __restrict__ Wm, float* __restrict__ dx,
-    float* __restrict__ dagg, float* __restrict__ part) {
-  // per wave: D (dout; dagg staging at the end), XH (prev, then LN-normalised x), DX, Ag, rstd
-  constexpr int PW = 3 * TR * L66 + TR * L34 + TR;
-  constexpr int NRED = 64 + 32 + 16;
-  static_assert(NRED * kW <= kWaves8 * PW, "reduction scratch");
-  __shared__ float WmL[FP * L80];      // WmL[o][i] = Wm[o][i]   (dout W_m)
-  __shared__ float WpL[FP * L48];      // WpL[o][j] = Wp[o][j]   (dx W_p; read transposed for x)
-  __shared__ float tiles[kWaves8 * PW];
-  {
-    Stage<FP * FA, kThreads8> sp;
-    Stage<FP * FP, kThreads8> sm;
-    sp.load([&](int q) { return Wp[q]; });
-    sm.load([&](int q) { return Wm[q]; });
-    sp.store([&](int q, float v) { WpL[(q / FA) * L48 + q % FA] = v; });
-    sm.store([&](int q, float v) { WmL[(q / FP) * L80 + q % FP] = v; });
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & (kW - 1), wave = threadIdx.x / kW;
-  const int c = lane & 15, g = lane >> 4;
-  float* D = tiles + wave * PW;
-  float* XH = D + TR * L66;
-  float* DX = XH + TR * L66;
-  float* Ag = DX + TR * L66;
-  float* RSt = Ag + TR * L34;
-  float bpv[4], gv[4], bv[4];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-    bpv[nt] = bp[nt * 16 + c];
-    gv[nt] = gam[nt * 16 + c];
-    bv[nt] = bet[nt * 16 + c];
-  }
-  f32x4 dWm[4][4], dWp[4][2];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) {
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) dWm[mt][nt] = zero4();
-    dWp[mt][0] = dWp[mt][1] = zero4();
-  }
-  float dbm[4] = {0.f, 0.f, 0.f, 0.f}, dbp[4] = {0.f, 0.f, 0.f, 0.f};
-  float dg[4] = {0.f, 0.f, 0.f, 0.f}, dbt[4] = {0.f, 0.f, 0.f, 0.f};
-  const int64_t ntiles = (N + TR - 1) / TR;
-  const int64_t gw = int64_t(blockIdx.x) * kWaves8 + wave, nw = int64_t(gridDim.x) * kWaves8;
-  float4 va[2], vd[4], vp[4];  // next-tile register prefetch (see point_tail_fwd_kernel)
-  auto fetch = [&](int64_t tt) {
-    const int64_t r0 = tt * TR;
-    const int nr = int(N - r0 < TR ? N - r0 : TR);
-    rows_load<FA>(agg, FA, r0, nr, va, lane);
-    rows_load<FP>(dout, FP, r0, nr, vd, lane);
-    if (PREV) rows_load<FP>(prev, FP, r0, nr, vp, lane);
-  };
-  if (kBwdPf && gw < ntiles) fetch(gw);
-  for (int64_t t = gw; t < ntiles; t += nw) {
-    const int64_t row0 = t * TR;
-    const int nrows = int(N - row0 < TR ? N - row0 : TR);
-    if constexpr (!kBwdPf) fetch(t);
-    rows_to_lds<FA, L34>(Ag, va, lane);
-    rows_to_lds<FP, L66>(D, vd, lane);
-    if (PREV) rows_to_lds<FP, L66>(XH, vp, lane);
-    if (kBwdPf && t + nw < ntiles) fetch(t + nw);
-    wave_sync();
-    // recompute x (C layout): agg W_p^T (W_p read transposed from WpL) + b_p + prev
-    f32x4 xa[4] = {zero4(), zero4(), zero4(), zero4()};
-#pragma unroll
-    for (int s = 0; s < FA / 4; ++s) {
-      const float a = Ag[c * L34 + 4 * s + g];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) xa[nt] = mfma16(a, WpL[(nt * 16 + c) * L48 + 4 * s + g], xa[nt]);
-    }
-    if (PREV) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) xa[nt][r] += XH[(4 * g + r) * L66 + nt * 16 + c];
-      wave_sync();  // prev read before XH is overwritten
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int e = 4 * g + r;
-      float xr[4], s1 = 0.f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        xr[nt] = xa[nt][r] + bpv[nt];
-        s1 += xr[nt];
-      }
-      const float mean = sum16(s1) * (1.f / FP);
-      float q = 0.f;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) q = fmaf(xr[nt] - mean, xr[nt] - mean, q);
-      const float rstd = rsq_normal(sum16(q) * (1.f / FP) + eps);
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) XH[e * L66 + nt * 16 + c] = (xr[nt] - mean) * rstd;
-      if (c == 0) RSt[e] = rstd;
-    }
-    wave_sync();
-    // d relu-out = dout W_m; LayerNorm backward; dx = dout + ... (rows past nrows: dout is 0)
-    f32x4 dph[4] = {zero4(), zero4(), zero4(), zero4()};
-#pragma unroll
-    for (int s = 0; s < FP / 4; ++s) {
-      const float a = D[c * L66 + 4 * s + g];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) dph[nt] = mfma16(a, WmL[(4 * s + g) * L80 + nt * 16 + c], dph[nt]);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int e = 4 * g + r;
-      float xr[4], o[4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) xr[nt] = XH[e * L66 + nt * 16 + c];
-      const float dh[4] = {dph[0][r], dph[1][r], dph[2][r], dph[3][r]};
-      ln_relu_bwd_row(xr, dh, gv, bv, RSt[e], dg, dbt, o);
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) DX[e * L66 + nt * 16 + c] = e < nrows ? o[nt] + D[e * L66 + nt * 16 + c] : 0.f;
-    }
-    wave_sync();
-    // dW_m += dout^T relu(LN x), dW_p += dx^T agg, biases (rows past nrows: dout, dx, agg are 0)
-#ifndef GASFM_PT_NODW
-#pragma unroll 1
-    for (int s = 0; s < TR / 4; ++s) {
-      const int row = 4 * s + g;
-      float ph[4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) ph[nt] = fmaxf(fmaf(XH[row * L66 + nt * 16 + c], gv[nt], bv[nt]), 0.f);
-      const float ag[2] = {Ag[row * L34 + c], Ag[row * L34 + 16 + c]};
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const float a = D[row * L66 + mt * 16 + c];
-        dbm[mt] += a;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) dWm[mt][nt] = mfma16(a, ph[nt], dWm[mt][nt]);
-        const float a2 = DX[row * L66 + mt * 16 + c];
-        dbp[mt] += a2;
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) dWp[mt][nt] = mfma16(a2, ag[nt], dWp[mt][nt]);
-      }
-    }
-#endif
-    // dagg = dx W_p, staged into D (dead) as 16 x 32
-    f32x4 da[2] = {zero4(), zero4()};
-#pragma unroll
-    for (int s = 0; s < FP / 4; ++s) {
-      const float a = DX[c * L66 + 4 * s + g];
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) da[nt] = mfma16(a, WpL[(4 * s + g) * L48 + nt * 16 + c], da[nt]);
-    }
-    wave_sync();
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) D[(4 * g + r) * L34 + nt * 16 + c] = da[nt][r];
-    wave_sync();
-    {
-      float4 vx[4], vg[2];
-      rows_from_lds<FP, L66>(DX, vx, lane);
-      rows_from_lds<FA, L34>(D, vg, lane);
-      rows_store<FP>(dx, FP, row0, nrows, vx, lane);
-      rows_store<FA>(dagg, FA, row0, nrows, vg, lane);
-    }
-    wave_sync();
-  }
-  float v[NRED];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) v[(mt * 4 + nt) * 4 + r] = dWm[mt][nt][r];
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) v[64 + (mt * 2 + nt) * 4 + r] = dWp[mt][nt][r];
-    }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    v[96 + k] = dbm[k];
-    v[100 + k] = dbp[k];
-    v[104 + k] = dg[k];
-    v[108 + k] = dbt[k];
-  }
-#ifndef GASFM_PT_NORED
-  wg_reduce_ordered<NRED, kWaves8, kWaves8 * PW>(v, tiles, wave, lane);
-#endif
-  if (wave == 0) {
-    float* out = part + int64_t(blockIdx.x) * TAIL_PART;
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int o = mt * 16 + 4 * g + r;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) out[o * FP + nt * 16 + c] = v[(mt * 4 + nt) * 4 + r];
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) out[FP * FP + o * FA + nt * 16 + c] = v[64 + (mt * 2 + nt) * 4 + r];
-      }
-    float tt[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) tt[k] = sum_groups(v[96 + k]);
-    if (g == 0) {
-      float* o = out + FP * FP + FP * FA;
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o[q * FP + k * 16 + c] = tt[q * 4 + k];
-    }
-  }
-}
-
-// ----------------------------------------------------------------------------- hub
-// With the C part (the usual case) 8 waves share the 50 KB of staged weights: 121 KB of LDS, one
-// workgroup = 2 waves per SIMD (4 waves were 1 per SIMD at 87 KB).
-template <bool HC>
-__global__ __launch_bounds__(HC ? kThreads8 : kThreads) void point_hub_fwd_kernel(
-    const float* __restrict__ X, int64_t N, float eps, const float* __restrict__ gA, const float* __restrict__ bA,
-    const float* __restrict__ WA, float* __restrict__ SA, const float* __restrict__ WB,
-    const float* __restrict__ bB, float* __restrict__ XL, const float* __restrict__ gC,
-    const float* __restrict__ bC, const float* __restrict__ WC, const float* __restrict__ bWC,
-    const float* __restrict__ WD, const float* __restrict__ bD, float* __restrict__ XR) {
-  constexpr int NW = HC ? kWaves8 : kWaves, NT = NW * kW;
-  constexpr int PW = TR * L66 + 2 * TR * L34 + 2 * TR;  // Raw (then XL staging), Tt (t, then XR), So (SA), MS, RS
-  __shared__ float WAt[FP * L48];               // WAt[k][j] = W_A[j][k]
-  __shared__ float WBt[FP * L80];               // WBt[k][o] = W_B[o][k]
-  __shared__ float WCt[HC ? FP * L48 : 1];      // WCt[k][j] = W_C[j][k]
-  __shared__ float WDt[HC ? FA * L48 : 1];      // WDt[k][j] = W_D[j][k]
-  __shared__ float GB[4 * FP];                  // gamma_A beta_A gamma_C beta_C
-  __shared__ float tiles[NW * PW];
-  {
-    Stage<FA * FP, NT> sa, sc;
-    Stage<FP * FP, NT> sb;
-    Stage<FA * FA, NT> sd;
-    sa.load([&](int q) { return WA[q]; });
-    sb.load([&](int q) { return WB[q]; });
-    if (HC) {
-      sc.load([&](int q) { return WC[q]; });
-      sd.load([&](int q) { return WD[q]; });
-    }
-    sa.store([&](int q, float v) { WAt[(q % FP) * L48 + q / FP] = v; });
-    sb.store([&](int q, float v) { WBt[(q % FP) * L80 + q / FP] = v; });
-    if (HC) {
-      sc.store([&](int q, float v) { WCt[(q % FP) * L48 + q / FP] = v; });
-      sd.store([&](int q, float v) { WDt[(q % FA) * L48 + q / FA] = v; });
-    }
-  }
-  if (threadIdx.x < FP) {
-    GB[threadIdx.x] = gA[threadIdx.x];
-    GB[FP + threadIdx.x] = bA[threadIdx.x];
-    GB[2 * FP + threadIdx.x] = HC ? gC[threadIdx.x] : 0.f;
-    GB[3 * FP + threadIdx.x] = HC ? bC[threadIdx.x] : 0.f;
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & (kW - 1), wave = threadIdx.x / kW;
-  const int c = lane & 15, g = lane >> 4;
-  float* Raw = tiles + wave * PW;
-  float* Tt = Raw + TR * L66;
-  float* So = Tt + TR * L34;
-  float* MS = So + TR * L34;
-  float* RS = MS + TR;
-  float bBv[4], bCv[2], bDv[2];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) bBv[nt] = bB[nt * 16 + c];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    bCv[nt] = HC ? bWC[nt * 16 + c] : 0.f;
-    bDv[nt] = HC ? bD[nt * 16 + c] : 0.f;
-  }
-  const int64_t ntiles = (N + TR - 1) / TR;
-  const int64_t gw = int64_t(blockIdx.x) * NW + wave, nw = int64_t(gridDim.x) * NW;
-  float4 vx[4];  // next-tile register prefetch (see point_tail_fwd_kernel)
-  auto fetch = [&](int64_t tt) {
-    const int64_t r0 = tt * TR;
-    rows_load<FP>(X, FP, r0, int(N - r0 < TR ? N - r0 : TR), vx, lane);
-  };
-  if (kFwdPf && gw < ntiles) fetch(gw);
-  for (int64_t t = gw; t < ntiles; t += nw) {
-    const int64_t row0 = t * TR;
-    const int nrows = int(N - row0 < TR ? N - row0 : TR);
-    if constexpr (!kFwdPf) fetch(t);
-    row_stats64(vx, eps, MS, RS, lane);
-    rows_to_lds<FP, L66>(Raw, vx, lane);
-    if (kFwdPf && t + nw < ntiles) fetch(t + nw);
-    wave_sync();
-    const float mi = MS[c], ri = RS[c];
-    f32x4 accB[4] = {zero4(), zero4(), zero4(), zero4()}, accA[2] = {zero4(), zero4()}, accC[2] = {zero4(), zero4()};
-#pragma unroll
-    for (int s = 0; s < FP / 4; ++s) {
-      const int k = 4 * s + g;
-      const float a = Raw[c * L66 + k];
-      const float xh = (a - mi) * ri;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) accB[nt] = mfma16(a, WBt[k * L80 + nt * 16 + c], accB[nt]);
-      const float pa = fmaxf(fmaf(xh, GB[k], GB[FP + k]), 0.f);
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) accA[nt] = mfma16(pa, WAt[k * L48 + nt * 16 + c], accA[nt]);
-      if (HC) {
-        const float pc = fmaxf(fmaf(xh, GB[2 * FP + k], GB[3 * FP + k]), 0.f);
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) accC[nt] = mfma16(pc, WCt[k * L48 + nt * 16 + c], accC[nt]);
-      }
-    }
-    wave_sync();  // Raw reads done: it becomes the XL staging tile
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int e = 4 * g + r;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) Raw[e * L66 + nt * 16 + c] = accB[nt][r] + bBv[nt];
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        So[e * L34 + nt * 16 + c] = accA[nt][r];
-        if (HC) Tt[e * L34 + nt * 16 + c] = accC[nt][r] + bCv[nt];
-      }
-    }
-    wave_sync();
-    f32x4 accD[2] = {zero4(), zero4()};
-    if (HC) {
-#pragma unroll
-      for (int s = 0; s < FA / 4; ++s) {
-        const float a = Tt[c * L34 + 4 * s + g];
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) accD[nt] = mfma16(a, WDt[(4 * s + g) * L48 + nt * 16 + c], accD[nt]);
-      }
-    }
-    {
-      float4 vl[4], vs[2];
-      rows_from_lds<FP, L66>(Raw, vl, lane);
-      rows_from_lds<FA, L34>(So, vs, lane);
-      rows_store<FP>(XL, FP, row0, nrows, vl, lane);
-      rows_store<FA>(SA, FA, row0, nrows, vs, lane);
-    }
-    if (HC) {
-      wave_sync();  // t reads done: Tt becomes the XR staging tile
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) Tt[(4 * g + r) * L34 + nt * 16 + c] = accD[nt][r] + bDv[nt];
-      wave_sync();
-      float4 vr[2];
-      rows_from_lds<FA, L34>(Tt, vr, lane);
-      rows_store<FA>(XR, FA, row0, nrows, vr, lane);
-    }
-    wave_sync();
-  }
-}
-
-// The hub backward runs as two passes, each adding its terms to the incoming gradient of p:
-//   C pass:  dq = dRes + LN_C_bwd(mask (dt W_C)),  dt = dXR W_D       partials HC_* layout
-//   AB pass: dp = dq + dXL W_B + LN_A_bwd(mask (dSA W_A))               partials HA_* layout
-// (one pass would hold 144 weight-gradient accumulators and spill at 2 waves per SIMD; the
-// split costs one extra write + read of dq).  dX may alias dRes: a tile's dRes rows are in LDS
-// before any of its dX rows is stored.
+// partial-row layouts (floats), one row per workgroup of a backward kernel
+constexpr int TAIL_PART = FP * FP + FP * FA + 4 * FP;  // dWm dWp dbm dbp dgam dbet
+// hub, part_a: dW_A [32 x 64] | dW_B [64 x 64] | db_B | dgamma_A | dbeta_A
 constexpr int HA_WA = 0, HA_WB = HA_WA + FA * FP, HA_BB = HA_WB + FP * FP, HA_GA = HA_BB + FP, HA_BA = HA_GA + FP,
               HA_PART = HA_BA + FP;
+// hub, part_c: dW_C [32 x 64] | dW_D [32 x 32] | db_C | db_D | dgamma_C | dbeta_C
 constexpr int HC_WC = 0, HC_WD = HC_WC + FA * FP, HC_BC = HC_WD + FA * FA, HC_BD = HC_BC + FA, HC_GC = HC_BD + FA,
               HC_BCL = HC_GC + FP, HC_PART = HC_BCL + FP;
 
-template <bool HR>
-__global__ __launch_bounds__(kThreads8) void point_hub_bwd_ab_kernel(
-    const float* __restrict__ X, int64_t N, float eps, const float* __restrict__ gA, const float* __restrict__ bA,
-    const float* __restrict__ WA, const float* __restrict__ WB, const float* __restrict__ dSA,
-    const float* __restrict__ dXL, const float* dRes, float* dX, float* __restrict__ part) {
-  constexpr int PW = 3 * TR * L66 + TR * L34 + 2 * TR;  // Raw, XLt (dXL), DXo (dRes, then dX), SAt (dSA), MS, RS
-  constexpr int NRED = 96 + 12;
-  static_assert(NRED * kW <= kWaves8 * PW, "reduction scratch");
-  __shared__ float WAl[FA * L80];        // W_A [32 x 64] row-major
-  __shared__ float WBl[FP * L80];        // W_B [64 x 64]
-  __shared__ float GB[2 * FP];           // gamma_A beta_A
-  __shared__ float tiles[kWaves8 * PW];
-  {
-    Stage<FA * FP, kThreads8> sa;
-    Stage<FP * FP, kThreads8> sb;
-    sa.load([&](int q) { return WA[q]; });
-    sb.load([&](int q) { return WB[q]; });
-    sa.store([&](int q, float v) { WAl[(q / FP) * L80 + q % FP] = v; });
-    sb.store([&](int q, float v) { WBl[(q / FP) * L80 + q % FP] = v; });
-  }
-  if (threadIdx.x < FP) {
-    GB[threadIdx.x] = gA[threadIdx.x];
-    GB[FP + threadIdx.x] = bA[threadIdx.x];
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & (kW - 1), wave = threadIdx.x / kW;
-  const int c = lane & 15, g = lane >> 4;
-  float* Raw = tiles + wave * PW;
-  float* XLt = Raw + TR * L66;
-  float* DXo = XLt + TR * L66;
-  float* SAt = DXo + TR * L66;
-  float* MS = SAt + TR * L34;
-  float* RS = MS + TR;
-  f32x4 dWA[2][4], dWB[4][4];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-    dWA[0][nt] = dWA[1][nt] = zero4();
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) dWB[mt][nt] = zero4();
-  }
-  float dbB[4] = {0.f, 0.f, 0.f, 0.f}, dgA[4] = {0.f, 0.f, 0.f, 0.f}, dbA[4] = {0.f, 0.f, 0.f, 0.f};
-  const int64_t ntiles = (N + TR - 1) / TR;
-  const int64_t gw = int64_t(blockIdx.x) * kWaves8 + wave, nw = int64_t(gridDim.x) * kWaves8;
-  float4 vx[4], vl[4], vs[2], vr[4];  // next-tile register prefetch (see point_tail_fwd_kernel)
-  auto fetch = [&](int64_t tt) {
-    const int64_t r0 = tt * TR;
-    const int nr = int(N - r0 < TR ? N - r0 : TR);
-    rows_load<FP>(X, FP, r0, nr, vx, lane);
-    rows_load<FP>(dXL, FP, r0, nr, vl, lane);
-    rows_load<FA>(dSA, FA, r0, nr, vs, lane);
-    if (HR) rows_load<FP>(dRes, FP, r0, nr, vr, lane);
-  };
-  if (kBwdPf && gw < ntiles) fetch(gw);
-  for (int64_t t = gw; t < ntiles; t += nw) {
-    const int64_t row0 = t * TR;
-    const int nrows = int(N - row0 < TR ? N - row0 : TR);
-    if constexpr (!kBwdPf) fetch(t);
-    row_stats64(vx, eps, MS, RS, lane);
-    rows_to_lds<FP, L66>(Raw, vx, lane);
-    rows_to_lds<FP, L66>(XLt, vl, lane);
-    rows_to_lds<FA, L34>(SAt, vs, lane);
-    if (HR) rows_to_lds<FP, L66>(DXo, vr, lane);
-    if (kBwdPf && t + nw < ntiles) fetch(t + nw);
-    wave_sync();
-    // weight gradients over the tile's rows (row = 4s + g; rows past nrows: dSA, dXL are 0)
-#pragma unroll 1
-    for (int s = 0; s < TR / 4; ++s) {
-      const int row = 4 * s + g;
-      const float mr = MS[row], rr = RS[row];
-      float xr[4], pa[4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        xr[nt] = Raw[row * L66 + nt * 16 + c];
-        pa[nt] = fmaxf(fmaf((xr[nt] - mr) * rr, GB[nt * 16 + c], GB[FP + nt * 16 + c]), 0.f);
-      }
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const float a = SAt[row * L34 + mt * 16 + c];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) dWA[mt][nt] = mfma16(a, pa[nt], dWA[mt][nt]);
-      }
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const float a = XLt[row * L66 + mt * 16 + c];
-        dbB[mt] += a;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) dWB[mt][nt] = mfma16(a, xr[nt], dWB[mt][nt]);
-      }
-    }
-    // data gradient (C layout: row 4g+r, column nt*16+c)
-    f32x4 dxb[4] = {zero4(), zero4(), zero4(), zero4()}, dp[4] = {zero4(), zero4(), zero4(), zero4()};
-#pragma unroll
-    for (int s = 0; s < FP / 4; ++s) {
-      const float a = XLt[c * L66 + 4 * s + g];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) dxb[nt] = mfma16(a, WBl[(4 * s + g) * L80 + nt * 16 + c], dxb[nt]);
-    }
-#pragma unroll
-    for (int s = 0; s < FA / 4; ++s) {
-      const float a = SAt[c * L34 + 4 * s + g];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) dp[nt] = mfma16(a, WAl[(4 * s + g) * L80 + nt * 16 + c], dp[nt]);
-    }
-    float gc[4], bc[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      gc[nt] = GB[nt * 16 + c];
-      bc[nt] = GB[FP + nt * 16 + c];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int e = 4 * g + r;
-      const float me = MS[e], re = RS[e];
-      float xh[4], t1[4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) xh[nt] = (Raw[e * L66 + nt * 16 + c] - me) * re;
-      const float dh[4] = {dp[0][r], dp[1][r], dp[2][r], dp[3][r]};
-      ln_relu_bwd_row(xh, dh, gc, bc, re, dgA, dbA, t1);
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        float* d = DXo + e * L66 + nt * 16 + c;
-        *d = dxb[nt][r] + t1[nt] + (HR ? *d : 0.f);
-      }
-    }
-    wave_sync();
-    {
-      float4 vo[4];
-      rows_from_lds<FP, L66>(DXo, vo, lane);
-      rows_store<FP>(dX, FP, row0, nrows, vo, lane);
-    }
-    wave_sync();
-  }
-  float v[NRED];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) v[(mt * 4 + nt) * 4 + r] = dWA[mt][nt][r];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) v[32 + (mt * 4 + nt) * 4 + r] = dWB[mt][nt][r];
-    }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    v[96 + k] = dbB[k];
-    v[100 + k] = dgA[k];
-    v[104 + k] = dbA[k];
-  }
-#ifndef GASFM_PT_NORED
-  wg_reduce_ordered<NRED, kWaves8, kWaves8 * PW>(v, tiles, wave, lane);
-#endif
-  if (wave == 0) {
-    float* out = part + int64_t(blockIdx.x) * HA_PART;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) out[HA_WA + (mt * 16 + 4 * g + r) * FP + nt * 16 + c] = v[(mt * 4 + nt) * 4 + r];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-          out[HA_WB + (mt * 16 + 4 * g + r) * FP + nt * 16 + c] = v[32 + (mt * 4 + nt) * 4 + r];
-      }
-    float tt[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) tt[k] = sum_groups(v[96 + k]);
-    if (g == 0) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        out[HA_BB + k * 16 + c] = tt[k];
-        out[HA_GA + k * 16 + c] = tt[4 + k];
-        out[HA_BA + k * 16 + c] = tt[8 + k];
-      }
-    }
-  }
-}
-
-template <bool HR>
-__global__ __launch_bounds__(kThreads8) void point_hub_bwd_c_kernel(
-    const float* __restrict__ X, int64_t N, float eps, const float* __restrict__ gC, const float* __restrict__ bC,
-    const float* __restrict__ WC, const float* __restrict__ bWC, const float* __restrict__ WD,
-    const float* __restrict__ dXR, const float* dRes, float* dX, float* __restrict__ part) {
-  // per wave: Raw, DXo (dRes, then dX), XRt (dXR), Dt (dt), Tt (t), MS, RS
-  constexpr int PW = 2 * TR * L66 + 3 * TR * L34 + 2 * TR;
-  constexpr int NRED = 48 + 12;
-  static_assert(NRED * kW <= kWaves8 * PW, "reduction scratch");
-  __shared__ float WCl[FA * L80];        // W_C [32 x 64]
-  __shared__ float WCt[FP * L48];        // W_C^T
-  __shared__ float WDl[FA * L48];        // W_D [32 x 32]
-  __shared__ float GB[2 * FP];           // gamma_C beta_C
-  __shared__ float tiles[kWaves8 * PW];
-  {
-    Stage<FA * FP, kThreads8> sc;
-    Stage<FA * FA, kThreads8> sd;
-    sc.load([&](int q) { return WC[q]; });
-    sd.load([&](int q) { return WD[q]; });
-    sc.store([&](int q, float v) {
-      WCl[(q / FP) * L80 + q % FP] = v;
-      WCt[(q % FP) * L48 + q / FP] = v;
-    });
-    sd.store([&](int q, float v) { WDl[(q / FA) * L48 + q % FA] = v; });
-  }
-  if (threadIdx.x < FP) {
-    GB[threadIdx.x] = gC[threadIdx.x];
-    GB[FP + threadIdx.x] = bC[threadIdx.x];
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & (kW - 1), wave = threadIdx.x / kW;
-  const int c = lane & 15, g = lane >> 4;
-  float* Raw = tiles + wave * PW;
-  float* DXo = Raw + TR * L66;
-  float* XRt = DXo + TR * L66;
-  float* Dt = XRt + TR * L34;
-  float* Tt = Dt + TR * L34;
-  float* MS = Tt + TR * L34;
-  float* RS = MS + TR;
-  const float bWCv[2] = {bWC[c], bWC[16 + c]};
-  f32x4 dWC[2][4], dWD[2][2];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) dWC[mt][nt] = zero4();
-    dWD[mt][0] = dWD[mt][1] = zero4();
-  }
-  float dbC[2] = {0.f, 0.f}, dbD[2] = {0.f, 0.f}, dgC[4] = {0.f, 0.f, 0.f, 0.f}, dbCl[4] = {0.f, 0.f, 0.f, 0.f};
-  const int64_t ntiles = (N + TR - 1) / TR;
-  const int64_t gw = int64_t(blockIdx.x) * kWaves8 + wave, nw = int64_t(gridDim.x) * kWaves8;
-  float4 vx[4], vq[2], vr[4];  // next-tile register prefetch (see point_tail_fwd_kernel)
-  auto fetch = [&](int64_t tt) {
-    const int64_t r0 = tt * TR;
-    const int nr = int(N - r0 < TR ? N - r0 : TR);
-    rows_load<FP>(X, FP, r0, nr, vx, lane);
-    rows_load<FA>(dXR, FA, r0, nr, vq, lane);
-    if (HR) rows_load<FP>(dRes, FP, r0, nr, vr, lane);
-  };
-  if (kBwdPf && gw < ntiles) fetch(gw);
-  for (int64_t t = gw; t < ntiles; t += nw) {
-    const int64_t row0 = t * TR;
-    const int nrows = int(N - row0 < TR ? N - row0 : TR);
-    if constexpr (!kBwdPf) fetch(t);
-    row_stats64(vx, eps, MS, RS, lane);
-    rows_to_lds<FP, L66>(Raw, vx, lane);
-    rows_to_lds<FA, L34>(XRt, vq, lane);
-    if (HR) rows_to_lds<FP, L66>(DXo, vr, lane);
-    if (kBwdPf && t + nw < ntiles) fetch(t + nw);
-    wave_sync();
-    const float mi = MS[c], ri = RS[c];
-    // t = W_C relu(LN_C p) + b_C (recomputed), dt = dXR W_D
-    f32x4 ta[2] = {zero4(), zero4()}, da[2] = {zero4(), zero4()};
-#pragma unroll
-    for (int s = 0; s < FP / 4; ++s) {
-      const int k = 4 * s + g;
-      const float pc = fmaxf(fmaf((Raw[c * L66 + k] - mi) * ri, GB[k], GB[FP + k]), 0.f);
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) ta[nt] = mfma16(pc, WCt[k * L48 + nt * 16 + c], ta[nt]);
-    }
-#pragma unroll
-    for (int s = 0; s < FA / 4; ++s) {
-      const float a = XRt[c * L34 + 4 * s + g];
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) da[nt] = mfma16(a, WDl[(4 * s + g) * L48 + nt * 16 + c], da[nt]);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        Tt[(4 * g + r) * L34 + nt * 16 + c] = ta[nt][r] + bWCv[nt];
-        Dt[(4 * g + r) * L34 + nt * 16 + c] = da[nt][r];
-      }
-    wave_sync();
-    // dW_C += dt^T relu(LN_C p), dW_D += dXR^T t (row = 4s + g; rows past nrows: dXR, dt are 0)
-#pragma unroll
-    for (int s = 0; s < TR / 4; ++s) {
-      const int row = 4 * s + g;
-      const float mr = MS[row], rr = RS[row];
-      float pc[4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-        pc[nt] = fmaxf(fmaf((Raw[row * L66 + nt * 16 + c] - mr) * rr, GB[nt * 16 + c], GB[FP + nt * 16 + c]), 0.f);
-      const float tt[2] = {Tt[row * L34 + c], Tt[row * L34 + 16 + c]};
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const float a = Dt[row * L34 + mt * 16 + c];
-        dbC[mt] += a;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) dWC[mt][nt] = mfma16(a, pc[nt], dWC[mt][nt]);
-        const float a2 = XRt[row * L34 + mt * 16 + c];
-        dbD[mt] += a2;
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) dWD[mt][nt] = mfma16(a2, tt[nt], dWD[mt][nt]);
-      }
-    }
-    // data gradient: dq = dRes + LN_C_bwd(mask (dt W_C))
-    f32x4 dp[4] = {zero4(), zero4(), zero4(), zero4()};
-#pragma unroll
-    for (int s = 0; s < FA / 4; ++s) {
-      const float a = Dt[c * L34 + 4 * s + g];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) dp[nt] = mfma16(a, WCl[(4 * s + g) * L80 + nt * 16 + c], dp[nt]);
-    }
-    float gc[4], bc[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      gc[nt] = GB[nt * 16 + c];
-      bc[nt] = GB[FP + nt * 16 + c];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int e = 4 * g + r;
-      const float me = MS[e], re = RS[e];
-      float xh[4], t1[4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) xh[nt] = (Raw[e * L66 + nt * 16 + c] - me) * re;
-      const float dh[4] = {dp[0][r], dp[1][r], dp[2][r], dp[3][r]};
-      ln_relu_bwd_row(xh, dh, gc, bc, re, dgC, dbCl, t1);
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        float* d = DXo + e * L66 + nt * 16 + c;
-        *d = t1[nt] + (HR ? *d : 0.f);
-      }
-    }
-    wave_sync();
-    {
-      float4 vo[4];
-      rows_from_lds<FP, L66>(DXo, vo, lane);
-      rows_store<FP>(dX, FP, row0, nrows, vo, lane);
-    }
-    wave_sync();
-  }
-  float v[NRED];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) v[(mt * 4 + nt) * 4 + r] = dWC[mt][nt][r];
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) v[32 + (mt * 2 + nt) * 4 + r] = dWD[mt][nt][r];
-    }
-  v[48] = dbC[0];
-  v[49] = dbC[1];
-  v[50] = dbD[0];
-  v[51] = dbD[1];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    v[52 + k] = dgC[k];
-    v[56 + k] = dbCl[k];
-  }
-#ifndef GASFM_PT_NORED
-  wg_reduce_ordered<NRED, kWaves8, kWaves8 * PW>(v, tiles, wave, lane);
-#endif
-  if (wave == 0) {
-    float* out = part + int64_t(blockIdx.x) * HC_PART;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const int o = mt * 16 + 4 * g + r;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) out[HC_WC + o * FP + nt * 16 + c] = v[(mt * 4 + nt) * 4 + r];
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) out[HC_WD + o * FA + nt * 16 + c] = v[32 + (mt * 2 + nt) * 4 + r];
-      }
-    float tt[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) tt[k] = sum_groups(v[48 + k]);
-    if (g == 0) {
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        out[HC_BC + k * 16 + c] = tt[k];
-        out[HC_BD + k * 16 + c] = tt[2 + k];
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        out[HC_GC + k * 16 + c] = tt[4 + k];
-        out[HC_BCL + k * 16 + c] = tt[8 + k];
-      }
-    }
-  }
-}
-
 // ----------------------------------------------------------------------------- forward, register-resident
-// The forward kernels above stage every 16-row tile through LDS twice per layer (rows in, C layout
-// out, A layout back in).  Computing the TRANSPOSED products Y^T = W X^T instead keeps a tile in
-// registers from load to store: with A = W and B = X^T, v_mfma_f32_16x16x4_f32 leaves lane
+// Computing the TRANSPOSED products Y^T = W X^T keeps a 16-row tile in registers from load to
+// store (no LDS round trip between layers): with A = W and B = X^T, v_mfma_f32_16x16x4_f32 leaves lane
 // (g = lane>>4, c = lane&15) holding Y[row c][16 ot + 4 g + r] (r < 4) -- 16 features of row c --
 // and those registers are exactly the B operand of the next layer when its k index is permuted
 // to k = 16 u + 4 g + j at step (u, j) (any consistent k order gives the same sum).  The weights
@@ -946,9 +66,6 @@ __global__ __launch_bounds__(kThreads8) void point_hub_bwd_c_kernel(
 // ds_read_b128 per 4 MFMAs.  Rows load and store as float4 (64 B per row per slab).  Row
 // statistics: 16 values per lane, then a sum over the 4 lane groups.  Only weights live in LDS
 // (24-37 KB per workgroup), so occupancy is set by VGPRs.
-#ifndef GASFM_PT_FWD_T
-#define GASFM_PT_FWD_T 1
-#endif
 #ifndef GASFM_PT_FWD_T_MINW
 #define GASFM_PT_FWD_T_MINW 1
 #endif
@@ -1292,11 +409,7 @@ __global__ __launch_bounds__(NWV * kW) void point_tail_hub_fwd_t_kernel(
 // the second layout of a tensor comes from L1 / L2), the computed ones come out of the products
 // in the layout needed, and only dx, consumed by both kinds of product, goes through a per-wave
 // LDS transpose (16 x 64).  LDS holds the weight slabs and that transpose tile (~49 KB per
-// 4-wave workgroup, the old kernels staged every tile: ~150 KB per 8-wave workgroup), and no MFMA
-// operand of a row tile is read from LDS.
-#ifndef GASFM_PT_BWD_R
-#define GASFM_PT_BWD_R 1
-#endif
+// 4-wave workgroup), and no MFMA operand of a row tile is read from LDS.
 // 1: scheduling barriers between the phases of a tile (each phase's MFMAs and VALU work stay
 // together); 0: none (the compiler may interleave a phase's VALU with the next phase's MFMAs)
 #ifndef GASFM_PT_SCHED
@@ -1439,7 +552,7 @@ __device__ __forceinline__ void cl_ln_relu_bwd(const f32x4 (&xh)[4], const f32x4
 }
 
 // dx = dout + LN_bwd(mask * (dout W_m)) (== d prev), dagg = dx W_p; partial row per workgroup in the
-// TAIL_PART layout of point_tail_bwd_kernel.  Per tile: x = agg W_p^T (+ b_p + prev) in C layout
+// TAIL_PART layout.  Per tile: x = agg W_p^T (+ b_p + prev) in C layout
 // (agg T-layout as A), h = relu(LN x); dh = dout W_m in C layout (dout T-layout as A); dx (C);
 // dW_m += dout^T h and dW_p += dx^T agg from C-layout registers; dx -> T layout (LDS), stored;
 // dagg = dx W_p in T layout (dx as B), stored.
@@ -1602,7 +715,7 @@ __global__ __launch_bounds__(kThreadsR, GASFM_PT_BWD_R_MINW) void point_tail_bwd
   }
 }
 
-// The whole hub backward (the C and AB passes above) in ONE register-resident pass.  Per tile:
+// The whole hub backward in ONE register-resident pass.  Per tile:
 //   t   = W_C relu(LN_C p) + b_C                     C layout (relu(LN_C p) T-layout as A)
 //   dt  = dXR W_D                                    C layout (weight / bias gradients) and T layout
 //                                                    (the A operand of dt W_C), both from dXR (T)
@@ -1613,13 +726,10 @@ __global__ __launch_bounds__(kThreadsR, GASFM_PT_BWD_R_MINW) void point_tail_bwd
 // LDS copy of the tile (one write per row chunk, read just before use: the 256 architected VGPRs
 // of a wave could not also hold a second, C-layout load of every tile).  The LayerNorm statistics
 // come from the T rows and reach the C layout by lane shuffles.  dRes is read in the C layout at
-// the top of its tile (before the next tile's requests), dp stored from the C layout.  Both
-// passes' partial rows are written (HA_* into part_a, HC_* into part_c), so the colsums and the
-// Python side are those of the two-pass form.  Algorithmic bytes per row:
-// p 256 + dSA 128 + dXL 256 + dXR 128 + dRes 256 + dp 256 = 1,280 (the two passes: 2,048).
-#ifndef GASFM_PT_HUB_BWD_R
-#define GASFM_PT_HUB_BWD_R 1
-#endif
+// the top of its tile (before the next tile's requests), dp stored from the C layout.  Two
+// partial rows per workgroup: the A / B gradients in the HA_* layout into part_a, the C / D ones
+// in the HC_* layout into part_c.  Algorithmic bytes per row:
+// p 256 + dSA 128 + dXL 256 + dXR 128 + dRes 256 + dp 256 = 1,280.
 #ifndef GASFM_PT_HUB_BWD_R_MINW
 #define GASFM_PT_HUB_BWD_R_MINW 1
 #endif
@@ -1939,36 +1049,17 @@ __global__ __launch_bounds__(kThreadsR, GASFM_PT_HUB_BWD_R_MINW) void point_hub_
 int64_t tiles_of(int64_t N) { return (N + TR - 1) / TR; }
 
 template <class K>
-int grid4(K kernel, int64_t N) {
-  return resident_grid(reinterpret_cast<const void*>(kernel), kThreads, 0, tiles_of(N), kWaves);
-}
-template <class K>
 int gridT(K kernel, int64_t N) {
   return resident_grid(reinterpret_cast<const void*>(kernel), kThreadsT, 0, tiles_of(N), kWavesT);
 }
-template <class K>
-int grid8(K kernel, int64_t N) {
-  return resident_grid(reinterpret_cast<const void*>(kernel), kThreads8, 0, tiles_of(N), kWaves8);
-}
-
 template <class K>
 int gridR(K kernel, int64_t N) {
   return resident_grid(reinterpret_cast<const void*>(kernel), kThreadsR, 0, tiles_of(N), kWavesR);
 }
 int tail_bwd_grid(int64_t N, bool has_prev) {
-  if (GASFM_PT_BWD_R)
-    return has_prev ? gridR(&point_tail_bwd_r_kernel<true>, N) : gridR(&point_tail_bwd_r_kernel<false>, N);
-  return has_prev ? grid8(&point_tail_bwd_kernel<true>, N) : grid8(&point_tail_bwd_kernel<false>, N);
+  return has_prev ? gridR(&point_tail_bwd_r_kernel<true>, N) : gridR(&point_tail_bwd_r_kernel<false>, N);
 }
-int hub_ab_grid(int64_t N, bool hr) {
-  return hr ? grid8(&point_hub_bwd_ab_kernel<true>, N) : grid8(&point_hub_bwd_ab_kernel<false>, N);
-}
-int hub_c_grid(int64_t N, bool hr) {
-  return hr ? grid8(&point_hub_bwd_c_kernel<true>, N) : grid8(&point_hub_bwd_c_kernel<false>, N);
-}
-// the one-pass hub backward: both partial buffers have its grid's rows (whether dRes is given or not),
-// and the two-pass entry points launch that many workgroups too while it is the default (their
-// partial buffers come from gasfm_point_hub_part_shape)
+// the hub backward: both partial buffers have its grid's rows, whether dRes is given or not
 int hub_r_grid(int64_t N) { return gridR(&point_hub_bwd_r_kernel<true>, N); }
 
 }  // namespace
@@ -1981,12 +1072,12 @@ extern "C" int32_t gasfm_point_tail_part_shape(int64_t N, int32_t has_prev, int3
   return N > 0 ? tail_bwd_grid(N, has_prev != 0) : 0;
 }
 
-extern "C" int32_t gasfm_point_hub_part_shape(int64_t N, int32_t which, int32_t has_res, int32_t* cols) {
+// has_res is ignored: the rows do not depend on whether dRes is given
+extern "C" int32_t gasfm_point_hub_part_shape(int64_t N, int32_t which, int32_t /*has_res*/, int32_t* cols) {
   if (cols) *cols = which ? HC_PART : HA_PART;
-  if (N <= 0) return 0;
-  if (GASFM_PT_HUB_BWD_R) return hub_r_grid(N);
-  return which ? hub_c_grid(N, has_res != 0) : hub_ab_grid(N, has_res != 0);
+  return N > 0 ? hub_r_grid(N) : 0;
 }
+
 extern "C" int gasfm_point_tail_fwd(const float* prev, const float* agg, int64_t N, const float* Wp, const float* bp,
                                     const float* ln_w, const float* ln_b, float eps, const float* Wm,
                                     const float* bm, float* out, void* stream) {
@@ -1995,21 +1086,12 @@ extern "C" int gasfm_point_tail_fwd(const float* prev, const float* agg, int64_t
   GASFM_REQUIRE(agg && Wp && bp && ln_w && ln_b && Wm && bm && out, "gasfm_point_tail_fwd: null pointer");
   GASFM_REQUIRE(aligned16(agg) && (!prev || aligned16(prev)), "gasfm_point_tail_fwd: alignment");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (GASFM_PT_FWD_T) {
-    if (prev)
-      hipLaunchKernelGGL(point_tail_fwd_t_kernel<true>, dim3(gridT(&point_tail_fwd_t_kernel<true>, N)),
-                         dim3(kThreadsT), 0, st, prev, agg, N, Wp, bp, ln_w, ln_b, eps, Wm, bm, out);
-    else
-      hipLaunchKernelGGL(point_tail_fwd_t_kernel<false>, dim3(gridT(&point_tail_fwd_t_kernel<false>, N)),
-                         dim3(kThreadsT), 0, st, prev, agg, N, Wp, bp, ln_w, ln_b, eps, Wm, bm, out);
-    return launch_status("gasfm_point_tail_fwd");
-  }
   if (prev)
-    hipLaunchKernelGGL(point_tail_fwd_kernel<true>, dim3(grid4(&point_tail_fwd_kernel<true>, N)), dim3(kThreads), 0,
-                       st, prev, agg, N, Wp, bp, ln_w, ln_b, eps, Wm, bm, out);
+    hipLaunchKernelGGL(point_tail_fwd_t_kernel<true>, dim3(gridT(&point_tail_fwd_t_kernel<true>, N)),
+                       dim3(kThreadsT), 0, st, prev, agg, N, Wp, bp, ln_w, ln_b, eps, Wm, bm, out);
   else
-    hipLaunchKernelGGL(point_tail_fwd_kernel<false>, dim3(grid4(&point_tail_fwd_kernel<false>, N)), dim3(kThreads),
-                       0, st, prev, agg, N, Wp, bp, ln_w, ln_b, eps, Wm, bm, out);
+    hipLaunchKernelGGL(point_tail_fwd_t_kernel<false>, dim3(gridT(&point_tail_fwd_t_kernel<false>, N)),
+                       dim3(kThreadsT), 0, st, prev, agg, N, Wp, bp, ln_w, ln_b, eps, Wm, bm, out);
   return launch_status("gasfm_point_tail_fwd");
 }
 
@@ -2023,20 +1105,11 @@ extern "C" int gasfm_point_tail_bwd(const float* dout, const float* prev, const 
   GASFM_REQUIRE(aligned16(dout) && aligned16(agg), "gasfm_point_tail_bwd: alignment");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int gsz = tail_bwd_grid(N, prev != nullptr);
-  if (GASFM_PT_BWD_R) {
-    if (prev)
-      hipLaunchKernelGGL(point_tail_bwd_r_kernel<true>, dim3(gsz), dim3(kThreadsR), 0, st, dout, prev, agg, N, Wp,
-                         bp, ln_w, ln_b, eps, Wm, dx, dagg, part);
-    else
-      hipLaunchKernelGGL(point_tail_bwd_r_kernel<false>, dim3(gsz), dim3(kThreadsR), 0, st, dout, prev, agg, N, Wp,
-                         bp, ln_w, ln_b, eps, Wm, dx, dagg, part);
-    return launch_status("gasfm_point_tail_bwd");
-  }
   if (prev)
-    hipLaunchKernelGGL(point_tail_bwd_kernel<true>, dim3(gsz), dim3(kThreads8), 0, st, dout, prev, agg, N, Wp, bp,
+    hipLaunchKernelGGL(point_tail_bwd_r_kernel<true>, dim3(gsz), dim3(kThreadsR), 0, st, dout, prev, agg, N, Wp, bp,
                        ln_w, ln_b, eps, Wm, dx, dagg, part);
   else
-    hipLaunchKernelGGL(point_tail_bwd_kernel<false>, dim3(gsz), dim3(kThreads8), 0, st, dout, prev, agg, N, Wp, bp,
+    hipLaunchKernelGGL(point_tail_bwd_r_kernel<false>, dim3(gsz), dim3(kThreadsR), 0, st, dout, prev, agg, N, Wp, bp,
                        ln_w, ln_b, eps, Wm, dx, dagg, part);
   return launch_status("gasfm_point_tail_bwd");
 }
@@ -2052,21 +1125,12 @@ extern "C" int gasfm_point_hub_fwd(const float* X, int64_t N, float eps, const f
   GASFM_REQUIRE(!hc || (bC && WC && bWC && WD && bD && XR), "gasfm_point_hub_fwd: null pointer (C part)");
   GASFM_REQUIRE(aligned16(X), "gasfm_point_hub_fwd: alignment");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (GASFM_PT_FWD_T) {
-    if (hc)
-      hipLaunchKernelGGL(point_hub_fwd_t_kernel<true>, dim3(gridT(&point_hub_fwd_t_kernel<true>, N)), dim3(kThreadsT),
-                         0, st, X, N, eps, gA, bA, WA, SA, WB, bB, XL, gC, bC, WC, bWC, WD, bD, XR);
-    else
-      hipLaunchKernelGGL(point_hub_fwd_t_kernel<false>, dim3(gridT(&point_hub_fwd_t_kernel<false>, N)),
-                         dim3(kThreadsT), 0, st, X, N, eps, gA, bA, WA, SA, WB, bB, XL, gC, bC, WC, bWC, WD, bD, XR);
-    return launch_status("gasfm_point_hub_fwd");
-  }
   if (hc)
-    hipLaunchKernelGGL(point_hub_fwd_kernel<true>, dim3(grid8(&point_hub_fwd_kernel<true>, N)), dim3(kThreads8), 0,
-                       st, X, N, eps, gA, bA, WA, SA, WB, bB, XL, gC, bC, WC, bWC, WD, bD, XR);
+    hipLaunchKernelGGL(point_hub_fwd_t_kernel<true>, dim3(gridT(&point_hub_fwd_t_kernel<true>, N)), dim3(kThreadsT),
+                       0, st, X, N, eps, gA, bA, WA, SA, WB, bB, XL, gC, bC, WC, bWC, WD, bD, XR);
   else
-    hipLaunchKernelGGL(point_hub_fwd_kernel<false>, dim3(grid4(&point_hub_fwd_kernel<false>, N)), dim3(kThreads), 0,
-                       st, X, N, eps, gA, bA, WA, SA, WB, bB, XL, gC, bC, WC, bWC, WD, bD, XR);
+    hipLaunchKernelGGL(point_hub_fwd_t_kernel<false>, dim3(gridT(&point_hub_fwd_t_kernel<false>, N)),
+                       dim3(kThreadsT), 0, st, X, N, eps, gA, bA, WA, SA, WB, bB, XL, gC, bC, WC, bWC, WD, bD, XR);
   return launch_status("gasfm_point_hub_fwd");
 }
 
@@ -2108,42 +1172,6 @@ extern "C" int gasfm_point_tail_hub_fwd(const float* prev, const float* agg, int
   return launch_status("gasfm_point_tail_hub_fwd");
 }
 
-extern "C" int gasfm_point_hub_bwd_c(const float* X, int64_t N, float eps, const float* gC, const float* bC,
-                                     const float* WC, const float* bWC, const float* WD, const float* dXR,
-                                     const float* dRes, float* dX, float* part, void* stream) {
-  GASFM_REQUIRE(N >= 0, "gasfm_point_hub_bwd_c: N < 0");
-  if (N == 0) return GASFM_OK;
-  GASFM_REQUIRE(X && gC && bC && WC && bWC && WD && dXR && dX && part, "gasfm_point_hub_bwd_c: null pointer");
-  GASFM_REQUIRE(aligned16(X), "gasfm_point_hub_bwd_c: alignment");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool hr = dRes != nullptr;
-  if (hr)
-    hipLaunchKernelGGL(point_hub_bwd_c_kernel<true>, dim3((GASFM_PT_HUB_BWD_R ? hub_r_grid(N) : hub_c_grid(N, true))), dim3(kThreads8), 0, st, X, N, eps,
-                       gC, bC, WC, bWC, WD, dXR, dRes, dX, part);
-  else
-    hipLaunchKernelGGL(point_hub_bwd_c_kernel<false>, dim3((GASFM_PT_HUB_BWD_R ? hub_r_grid(N) : hub_c_grid(N, false))), dim3(kThreads8), 0, st, X, N,
-                       eps, gC, bC, WC, bWC, WD, dXR, dRes, dX, part);
-  return launch_status("gasfm_point_hub_bwd_c");
-}
-
-extern "C" int gasfm_point_hub_bwd_ab(const float* X, int64_t N, float eps, const float* gA, const float* bA,
-                                      const float* WA, const float* WB, const float* dSA, const float* dXL,
-                                      const float* dRes, float* dX, float* part, void* stream) {
-  GASFM_REQUIRE(N >= 0, "gasfm_point_hub_bwd_ab: N < 0");
-  if (N == 0) return GASFM_OK;
-  GASFM_REQUIRE(X && gA && bA && WA && WB && dSA && dXL && dX && part, "gasfm_point_hub_bwd_ab: null pointer");
-  GASFM_REQUIRE(aligned16(X), "gasfm_point_hub_bwd_ab: alignment");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool hr = dRes != nullptr;
-  if (hr)
-    hipLaunchKernelGGL(point_hub_bwd_ab_kernel<true>, dim3((GASFM_PT_HUB_BWD_R ? hub_r_grid(N) : hub_ab_grid(N, true))), dim3(kThreads8), 0, st, X, N,
-                       eps, gA, bA, WA, WB, dSA, dXL, dRes, dX, part);
-  else
-    hipLaunchKernelGGL(point_hub_bwd_ab_kernel<false>, dim3((GASFM_PT_HUB_BWD_R ? hub_r_grid(N) : hub_ab_grid(N, false))), dim3(kThreads8), 0, st, X, N,
-                       eps, gA, bA, WA, WB, dSA, dXL, dRes, dX, part);
-  return launch_status("gasfm_point_hub_bwd_ab");
-}
-
 extern "C" int gasfm_point_hub_bwd(const float* X, int64_t N, float eps, const float* gA, const float* bA,
                                    const float* WA, const float* WB, const float* gC, const float* bC,
                                    const float* WC, const float* bWC, const float* WD, const float* dSA,
@@ -2157,11 +1185,6 @@ extern "C" int gasfm_point_hub_bwd(const float* X, int64_t N, float eps, const f
   GASFM_REQUIRE(aligned16(X) && aligned16(dSA) && aligned16(dXL) && aligned16(dXR),
                 "gasfm_point_hub_bwd: alignment");
   GASFM_REQUIRE(dX != X && dX != dSA && dX != dXL && dX != dXR, "gasfm_point_hub_bwd: dX aliases an input");
-  if (!GASFM_PT_HUB_BWD_R) {  // the two-pass form: C pass into dX, AB pass in place
-    const int st = gasfm_point_hub_bwd_c(X, N, eps, gC, bC, WC, bWC, WD, dXR, dRes, dX, part_c, stream);
-    if (st != GASFM_OK) return st;
-    return gasfm_point_hub_bwd_ab(X, N, eps, gA, bA, WA, WB, dSA, dXL, dX, dX, part_a, stream);
-  }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int gsz = hub_r_grid(N);
   if (dRes)

@@ -13,8 +13,9 @@ read: an uninitialised 1x1 tensor, no fill kernel) whose gradient
 the epilogue's backward sets to dP' (the block-output gradient), so that the
 prologue's backward kernel can do the whole P-side backward in one pass:
   dP = LN_bwd(mask * (Wl^T dXL + Wp^T dP'/4)) + dP'      (identity residual, layers.py:254-261)
-For the 32-wide blocks the prologue and the camera-direction attention are one kernel
-(EdgeCamFn, csrc/edge_cam.hip).  Node-level work between them runs in the fused point /
+For the 32-wide blocks the prologue and the camera-direction attention are one kernel in each
+direction (EdgeCamFn, csrc/edge_cam.hip: gasfm_edge_cam_fwd, and gasfm_edge_cam_pbwd for the
+camera attention's and the prologue's backward together).  Node-level work between them runs in the fused point /
 view / global kernels (point_block.py, view_block.py, dense.py: csrc/point_block.hip,
 view_block.hip, global_vec.hip); only the camera side's two m x 1024 x 1024 GEMMs per block
 go through hipBLASLt (or the HIP MFMA GEMMs, view_block._mm).
@@ -28,9 +29,6 @@ from .attention import (attn_backward_raw, attn_forward_partial, attn_forward_ra
                         combine_fwd_l1, combine_partials)
 
 PROJ_SCALE = 0.25  # the "/ 4" of layers.py:945
-# EdgeCamFn's backward as ONE kernel (gasfm_edge_cam_pbwd: camera attention backward + edge
-# prologue backward, dXLc never stored); 0 selects the two kernels edge_cam_bwd + edge_prologue_bwd
-CAM_PBWD = os.environ.get("GASFM_CAM_PBWD", "1") != "0"
 # The edge epilogue's backward folded into edge_cam_pbwd (round 3): block b's lin_proj weight
 # gradient in block b's own edge_cam_pbwd (it holds dRes = dP' and relu(LN_b(P_b))), dSv / dP0 in
 # block b+1's (the kernel that produces dP').  0: edge_epilogue_bwd as before.
@@ -175,15 +173,6 @@ class EdgeCamFn(torch.autograd.Function):
         return _cam_backward(ctx, ctx.saved_tensors, dXLp, g_c, dRes)
 
 
-def _dwp_torch(P, ln_w, ln_b, eps, dRes, P0):
-    """The epilogue weight gradient scale dRes^T [relu(LN(P)) | P0] with torch ops (the EdgeCamFn
-    backward paths without edge_cam_pbwd)."""
-    ph = torch.relu(torch.nn.functional.layer_norm(P, (P.shape[1],), ln_w, ln_b, eps))
-    if P0 is not None:
-        ph = torch.cat([ph, P0], dim=1)
-    return PROJ_SCALE * (dRes.t() @ ph)
-
-
 def _cam_backward(ctx, saved, dXLp, g_c, dRes, epi=None, dXR=None):
     """EdgeCamFn's backward from its saved state (ctx attributes eps, heads, slope, plan, att_shape,
     has_ln, dwp, defer): the 20 input gradients of EdgeCamFn.forward.  epi: the previous block's
@@ -198,7 +187,8 @@ def _cam_backward(ctx, saved, dXLp, g_c, dRes, epi=None, dXR=None):
     dwp = ctx.dwp and dRes is not None and ln_w is not None
     ctx.epi_done = False
     dWp = None
-    if CAM_PBWD and plan.n_items:
+    o = 64 * 32  # [dW 64x32 | db 64 | dgamma 32 | dbeta 32 | ...] in the summed partial row
+    if plan.n_items:
         # camera attention backward + prologue backward in one kernel (gasfm_edge_cam_pbwd)
         if dXR is None:
             dXR = torch.empty((plan.num_targets, 32), dtype=torch.float32, device=dev)
@@ -222,44 +212,35 @@ def _cam_backward(ctx, saved, dXLp, g_c, dRes, epi=None, dXR=None):
         else:
             bwd_combine(plan, part_dxr, 32, dXR)
         tot = _native.param_colsum(part, ctx.defer)
-        o = 64 * 32
         ta = tot[o + 128:o + 192]
         if dwp:
             dWp = tot[o + 192:o + 192 + 32 * wcols].view(32, wcols)
     else:
-        # camera attention backward (XLc recomputed from P): dXLc, dXR, [datt | dbias] partials
-        dXLc = torch.empty((E, 32), dtype=torch.float32, device=dev)
+        # no local edges (a rank without camera items): zero dXR and [datt | dbias], and the
+        # prologue backward on a zero camera half dXLc
+        dXLc = torch.zeros((E, 32), dtype=torch.float32, device=dev)
         if dXR is None:
-            dXR = torch.empty((plan.num_targets, 32), dtype=torch.float32, device=dev)
-        part_dxr = torch.empty((plan.n_part_rows, 32), dtype=torch.float32, device=dev) if plan.n_slots else None
-        rows, cols = _native.edge_cam_bwd_part_shape(plan.n_items)
-        part_a = (torch.empty if plan.n_items else torch.zeros)((rows, cols), dtype=torch.float32, device=dev)
-        if plan.n_items:
-            _native.edge_cam_bwd(P, ln_w, ln_b, ctx.eps, Wc.contiguous(), bc.contiguous(), XR, attf, bias, ctx.slope,
-                                 out, smax, ssum, g_c, plan.items, plan.n_items, dXLc, dXR, part_dxr, part_a)
-            bwd_combine(plan, part_dxr, 32, dXR)
-        else:  # no local edges
-            dXLc.zero_()
+            dXR = torch.zeros((plan.num_targets, 32), dtype=torch.float32, device=dev)
+        else:
             dXR.zero_()
-        # prologue backward on [dXLp | dXLc] (+ the block output's residual gradient)
         dP = torch.empty_like(P)
-        prow = _native.edge_part_floats(0, E) // (64 * 32 + 64 + 64)
-        part = torch.empty((prow, 64 * 32 + 64 + 64), dtype=torch.float32, device=dev)
-        _native.edge_prologue_bwd(dXLp, P, dRes, ln_w, ln_b, ctx.eps, Wpt.contiguous(),
-                                  Wp.contiguous() if dRes is not None else None, PROJ_SCALE, dP, part, Wc.contiguous(),
-                                  dXLc=dXLc)
-        ta = _native.param_colsum(part_a, ctx.defer)
-        tot = _native.param_colsum(part, ctx.defer)
-        o = 64 * 32
+        if E:
+            prow = _native.edge_part_floats(0, E) // (o + 64 + 64)
+            part = torch.empty((prow, o + 64 + 64), dtype=torch.float32, device=dev)
+            _native.edge_prologue_bwd(dXLp, P, dRes, ln_w, ln_b, ctx.eps, Wpt.contiguous(),
+                                      Wp.contiguous() if dRes is not None else None, PROJ_SCALE, dP, part,
+                                      Wc.contiguous(), dXLc=dXLc)
+            tot = _native.param_colsum(part, ctx.defer)
+        else:  # nothing to launch on (the kernel's launcher rejects the null pointers of empty tensors)
+            tot = torch.zeros(o + 64 + 64, dtype=torch.float32, device=dev)
+        ta = torch.zeros(64, dtype=torch.float32, device=dev)
         if dwp:
-            dWp = _dwp_torch(P, ln_w, ln_b, ctx.eps, dRes, P0) if plan.n_items else torch.zeros_like(Wp)
-    if dwp and dWp is None:  # no local edges
-        dWp = torch.zeros_like(Wp)
+            dWp = torch.zeros_like(Wp)
     dW, db = tot[:o].view(64, 32), tot[o:o + 64]
     dgam = tot[o + 64:o + 96] if ctx.has_ln else None
     dbet = tot[o + 96:o + 128] if ctx.has_ln else None
     dbias = ta[32:]
-    if getattr(ctx, "sharded", False) or (CAM_PBWD and plan.n_items):
+    if getattr(ctx, "sharded", False) or plan.n_items:
         # edge_cam_pbwd leaves the bias gradient to this column sum of gout over all targets
         dbias = replicated_dbias(g_c, ctx.defer)
     return (dP, dgam, dbet, dW[:32], db[:32], dW[32:], db[32:], dWp, None, None, dXR,

@@ -752,7 +752,7 @@ class GraphAttnSfMLayer(Module):
         if gfu.cam_fusable(plans):
             holder = {}
             # the block's lin_proj gradient from its edge_cam_pbwd (edge_block.EPI_FOLD)
-            dwp = edge_block.EPI_FOLD and edge_block.CAM_PBWD and ln.weight is not None
+            dwp = edge_block.EPI_FOLD and ln.weight is not None
             attend = gfu.edge_cam_attend(P, ln.weight, ln.bias, ln.eps, pfu.lin_proj.weight, plans, holder,
                                          P0e if dwp else None, dwp)
             pts, view, glob = gfu.forward_fused(None, plans, prev_pt, prev_view, prev_glob, carry=carry, pfu=pfu,

@@ -137,21 +137,6 @@ int gasfm_edge_cam_fwd(const float* P, const float* ln_w, const float* ln_b, flo
                        const int32_t* pos, const float* XR, int64_t ldXR, const float* att, const float* bias,
                        float slope, const gasfm_work_item* items, int32_t n_items, int32_t finalize, float* out,
                        int64_t ldOut, float* seg_max, float* seg_sum, int64_t ldStat, float* part, void* stream);
-/* Backward of the camera attention above (gasfm_gat_attn_bwd on these items) with XLc recomputed
- * from P instead of read: given the camera aggregates' gradient gout and the forward's out /
- * seg_max / seg_sum, writes dXLc [E, 32] (row stride ldD; gasfm_edge_prologue_bwd's camera half),
- * dXR[seg] for complete items (split items: part_dxr[slot], merge with
- * gasfm_gat_attn_bwd_combine) and one partial row per workgroup
- * part[gasfm_edge_cam_bwd_part_rows(n_items), gasfm_edge_cam_bwd_part_cols()] = [datt 32 | dbias 32]
- * (reduce with gasfm_colsum). */
-int32_t gasfm_edge_cam_bwd_part_rows(int32_t n_items);
-int32_t gasfm_edge_cam_bwd_part_cols(void);
-int gasfm_edge_cam_bwd(const float* P, const float* ln_w, const float* ln_b, float eps, const float* Wc,
-                       const float* bc, const float* XR, int64_t ldXR, const float* att, const float* bias,
-                       float slope, const float* out, int64_t ldOut, const float* seg_max, const float* seg_sum,
-                       int64_t ldStat, const float* gout, int64_t ldG, const gasfm_work_item* items,
-                       int32_t n_items, float* dXLc, int64_t ldD, float* dXR, int64_t ldDXR, float* part_dxr,
-                       float* part, void* stream);
 
 /* Block b's edge epilogue and block b+1's edge prologue + camera-direction attention forward in ONE
  * pass over block b+1's camera plan items (gasfm_edge_epilogue_fwd of block b followed by
@@ -183,10 +168,14 @@ int gasfm_edge0_seam_fwd(const float* P, const int32_t* pt, const float* ln_a_w,
                          int32_t finalize, float* out, int64_t ldOut, float* seg_max, float* seg_sum, int64_t ldStat,
                          float* part, void* stream);
 
-/* The camera attention's backward and the block's edge prologue backward in ONE pass over the
- * camera plan's items (gasfm_edge_cam_bwd followed by gasfm_edge_prologue_bwd with dXLc, without
- * storing dXLc): dP [E, 32], dXR per camera (split items: part_dxr rows for
- * gasfm_gat_attn_bwd_combine), and per workgroup the partial row
+/* Backward of gasfm_edge_cam_fwd: the camera attention's backward (gasfm_gat_attn_bwd on these
+ * items, with XLc = Wc relu(LN(P)) + bc recomputed from P instead of read) and the block's edge
+ * prologue backward in ONE pass over the camera plan's items.  Given the camera aggregates'
+ * gradient gout (row stride ldG) and the forward's out / seg_max / seg_sum, the attention's
+ * gradient dXLc of XLc stays in registers and
+ *   dP = LN_bwd(relu_mask * (Wpt^T dXLp + Wc^T dXLc + scale Wp[:, :32]^T dRes)) + dRes
+ * is written as dP [E, 32], dXR[seg] per camera for complete items (split items: part_dxr[slot]
+ * rows, merged by gasfm_gat_attn_bwd_combine), and per workgroup the partial row
  * [dW 64x32 | db 64 | dgamma 32 | dbeta 32 | datt 32 | 0 (32)]; the attention bias gradient is the
  * column sum of gout over all targets (every target's output carries the bias), taken by the caller
  * (part[gasfm_edge_cam_pbwd_part_rows(n_items), gasfm_edge_cam_pbwd_part_cols()]).
@@ -376,7 +365,7 @@ int gasfm_edge_epilogue_bwd(const gasfm_work_item* items, int32_t n_items, const
 /* dP = LN_bwd(relu_mask * (W^T dXL + scale*Wp[:, :32]^T dRes)) + dRes, and the
  * per-workgroup partials of dW, db, dgamma, dbeta (LayerNorm/ReLU/lin_l backward).
  * dXLc != NULL: dXL holds only the point half ([E, >= 32], row stride ldX) and dXLc the camera
- * half ([E, >= 32], row stride ldC), as gasfm_edge_cam_bwd writes it. */
+ * half ([E, >= 32], row stride ldC). */
 int gasfm_edge_prologue_bwd(const float* dXL, int64_t ldX, const float* P, const float* dRes,
                             int64_t E, const float* ln_w, const float* ln_b, float eps,
                             const float* W, const float* W2, const float* Wp, int32_t ldWp,
@@ -464,10 +453,11 @@ int gasfm_node_ln_linear_bwd(const float* dY, const float* X, int64_t N, int32_t
  * [dWm 64x64 | dWp 64x32 | dbm 64 | dbp 64 | dgamma 64 | dbeta 64]. */
 int gasfm_point_tail_part_shape(int64_t N, int32_t has_prev, int32_t* cols);
 
-/* Partial buffer rows for gasfm_point_hub_bwd_ab (which = 0):
+/* Partial buffer rows for gasfm_point_hub_bwd; *cols receives the row width of part_a (which = 0):
  *   [dWA 32x64 | dWB 64x64 | dbB 64 | dgamma_A 64 | dbeta_A 64]
- * or gasfm_point_hub_bwd_c (which = 1):
- *   [dWC 32x64 | dWD 32x32 | dbWC 32 | dbD 32 | dgamma_C 64 | dbeta_C 64]. */
+ * or of part_c (which = 1):
+ *   [dWC 32x64 | dWD 32x32 | dbWC 32 | dbD 32 | dgamma_C 64 | dbeta_C 64].
+ * Both buffers have the same number of rows; has_res is ignored (kept for the ABI). */
 int gasfm_point_hub_part_shape(int64_t N, int32_t which, int32_t has_res, int32_t* cols);
 
 int gasfm_point_tail_fwd(const float* prev, const float* agg, int64_t N, const float* Wp, const float* bp,
@@ -495,20 +485,13 @@ int gasfm_point_tail_hub_fwd(const float* prev, const float* agg, int64_t N, con
                              const float* WC, const float* bWC, const float* WD, const float* bD, float* XR,
                              void* stream);
 
-/* dX = dRes + LN_C_bwd(mask (dXR WD WC)) (dRes may be null), partials. */
-int gasfm_point_hub_bwd_c(const float* X, int64_t N, float eps, const float* gC, const float* bC, const float* WC,
-                          const float* bWC, const float* WD, const float* dXR, const float* dRes, float* dX,
-                          float* part, void* stream);
-
-/* dX = dRes + dXL WB + LN_A_bwd(mask (dSA WA)) (dRes may be null), partials. */
-int gasfm_point_hub_bwd_ab(const float* X, int64_t N, float eps, const float* gA, const float* bA,
-                           const float* WA, const float* WB, const float* dSA, const float* dXL,
-                           const float* dRes, float* dX, float* part, void* stream);
-
-/* The whole hub backward in one pass (both of the above; the two-pass form when the library is
- * built with GASFM_PT_HUB_BWD_R=0): dX = dRes + dXL WB + LN_A_bwd(mask (dSA WA))
- * + LN_C_bwd(mask (dXR WD WC)); dRes may be null or alias dX, dX must not alias the other inputs.
- * part_a / part_c: the which = 0 / which = 1 partial layouts above, gasfm_point_hub_part_shape rows. */
+/* The hub backward, one pass over X = p [N x 64]:
+ *   dX = dRes + dXL WB + LN_A_bwd(mask_A (dSA WA)) + LN_C_bwd(mask_C ((dXR WD) WC))
+ * where mask_A / mask_C are the ReLU masks of LN_A(p) / LN_C(p), dSA [N x 32], dXL [N x 64] and
+ * dXR [N x 32] the gradients of the forward's three outputs and dRes [N x 64] the gradient of the
+ * identity output (the next block's state skip).  dRes may be null or alias dX; dX must not alias
+ * the other inputs.  part_a / part_c receive one partial row per workgroup in the which = 0 /
+ * which = 1 layouts of gasfm_point_hub_part_shape (its row count). */
 int gasfm_point_hub_bwd(const float* X, int64_t N, float eps, const float* gA, const float* bA, const float* WA,
                         const float* WB, const float* gC, const float* bC, const float* WC, const float* bWC,
                         const float* WD, const float* dSA, const float* dXL, const float* dXR, const float* dRes,

@@ -224,3 +224,37 @@ def test_block0_seam_vs_separate(device, monkeypatch):
         err = float((res[True][2][k] - g0).norm())
         own = float((g0 - torch.from_numpy(g64[k])).norm())
         assert err <= max(1e-3 * float(g0.norm()), 10 * own) + 1e-9, (k, err, own, float(g0.norm()))
+
+
+def test_edge_cam_fn_no_local_edges(device):
+    """A rank without local edges (E = 0, a camera plan without work items; m = 2 cameras,
+    H = 4, C = 8): EdgeCamFn's backward launches no camera-item kernel and returns gradients of
+    the right shapes, with dXR, datt and the folded lin_proj gradient dWp exactly zero.
+    (At b512b46 this backward raised: gasfm_edge_prologue_bwd rejected the null pointers of the
+    empty tensors.)"""
+    from gasfm_amd.distributed import ShardContext
+    m = 2
+    empty = lambda *s: torch.zeros(s, dtype=torch.int32)
+    plan = AttnPlan(empty(m + 1), None, empty(0, 4), empty(0, 4), 0, m, 0, 0).to(device)
+    assert plan.n_items == 0 and plan.num_targets == m
+    g = torch.Generator(device=device).manual_seed(11)
+    rnd = lambda *s, sc=1.0: (torch.randn(s, generator=g, device=device) * sc)
+    P, P0 = rnd(0, 32), rnd(0, 2)
+    ln_w, ln_b = 1 + 0.3 * rnd(32), 0.2 * rnd(32)
+    Wpt, Wc, Wp = rnd(32, 32, sc=0.2), rnd(32, 32, sc=0.2), rnd(32, 34, sc=0.2)
+    bpt, bc = rnd(32, sc=0.1), rnd(32, sc=0.1)
+    XR, att, bias = rnd(m, 32), rnd(1, 4, 8, sc=0.35), rnd(32, sc=0.1)
+    leaves = [P, ln_w, ln_b, Wpt, bpt, Wc, bc, XR, att, bias, Wp]
+    for t in leaves:
+        t.requires_grad_(True)
+    pos = torch.zeros(0, dtype=torch.int32, device=device)
+    shard = ShardContext(0, 1, emulate=True)  # one rank: the gathered partial rows are its own
+    XLp, out_c, token = EdgeCamFn.apply(P, ln_w, ln_b, Wpt, bpt, Wc, bc, Wp, 1e-5, pos, XR, att, bias, plan, 4, 0.2,
+                                        plan, shard, P0, True)
+    assert XLp.shape == (0, 32) and out_c.shape == (m, 32) and token.shape == (0, 32)
+    assert torch.equal(out_c.detach(), bias.detach().expand(m, 32))  # empty segments: out = bias
+    torch.autograd.backward([XLp, out_c, token], [rnd(0, 32), rnd(m, 32), rnd(0, 32)])
+    for t in leaves:
+        assert t.grad is not None and t.grad.shape == t.shape
+    for name, t in (("dXR", XR), ("datt", att), ("dWp", Wp)):
+        assert not t.grad.any(), name

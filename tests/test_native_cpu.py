@@ -193,18 +193,44 @@ def test_lazy_graph_wrappers_and_scene_csr():
 
 def test_binding_arity_matches_header():
     """Every ctypes signature in _native._SIGS has as many parameters as its declaration in
-    include/gasfm.h (a short argtypes list fails only at call time, on the GPU)."""
+    include/gasfm.h (a short argtypes list fails only at call time, on the GPU), and each
+    parameter's and the return value's ctypes type is the one the declared C type maps to."""
+    import ctypes
     import re
+    scalars = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+               "float": ctypes.c_float, "double": ctypes.c_double}
+
+    def ctype_of(decl, ret=False):
+        """ctypes type of a C parameter ('const float* X', 'int32_t n') or return type."""
+        if "*" in decl:
+            return ctypes.c_char_p if ret and re.fullmatch(r"const\s+char\s*\*", decl) else ctypes.c_void_p
+        words = [w for w in decl.split() if w != "const"]
+        if ret and words == ["void"]:
+            return None
+        return scalars[words[0]]  # an unmapped C type is a KeyError: extend the mapping on purpose
+
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "gasfm.h")).read(), flags=re.S)
-    bad = []
+    bad, bad_types, seen = [], [], set()
     for m in re.finditer(r"\b(gasfm_\w+)\s*\(([^;{]*?)\)\s*;", text):
         name, args = m.group(1), m.group(2).strip()
         if name not in _native._SIGS:
             continue
+        seen.add(name)
+        restype, argtypes = _native._SIGS[name]
+        params = [] if args in ("", "void") else [a.strip() for a in args.split(",")]
         n = 0 if args in ("", "void") else args.count(",") + 1
-        if n != len(_native._SIGS[name][1]):
-            bad.append((name, n, len(_native._SIGS[name][1])))
+        if n != len(argtypes):
+            bad.append((name, n, len(argtypes)))
+            continue
+        ret = re.search(r"([\w \t\*]+)$", text[:m.start(1)]).group(1).strip()
+        if ctype_of(ret, ret=True) is not restype:
+            bad_types.append((name, "return", ret, restype))
+        for i, (p, t) in enumerate(zip(params, argtypes)):
+            if ctype_of(p) is not t:
+                bad_types.append((name, i, p, t))
     assert not bad, bad
+    assert not bad_types, bad_types
+    assert seen == set(_native._SIGS), sorted(set(_native._SIGS) - seen)
 
 
 def test_gemm_smallm_ok_matches_documented_rule():

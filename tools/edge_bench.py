@@ -92,15 +92,9 @@ def main():
                                       b[32:].contiguous(), XLp, pp.pos, XRc, att, bias, 0.2, pc.items, pc.n_items,
                                       True, co, cmax, csum, cpart),
         E * (128 + 8 + 4 + 128 + 128 + 128 + 4) + (n + m) * 128)
-    dXLc, dXRc = torch.empty(E, 32, device=dev), torch.empty(m, 32, device=dev)
+    dXRc = torch.empty(m, 32, device=dev)
     pdxr = torch.empty(max(pc.n_part_rows, 1), 32, device=dev)
-    r_, c_ = _native.edge_cam_bwd_part_shape(pc.n_items)
-    cbp = torch.empty(r_, c_, device=dev)
     gout = rnd(m, 32)
-    run("edge_cam_bwd(LN)",
-        lambda: _native.edge_cam_bwd(P, ln_w, ln_b, 1e-5, W[32:].contiguous(), b[32:].contiguous(), XRc, att, bias,
-                                     0.2, co, cmax, csum, gout, pc.items, pc.n_items, dXLc, dXRc, pdxr, cbp),
-        E * (128 + 128) + m * 256)
     dXLp_in, dRes_in = rnd(E, 32), rnd(E, 32)
     rp, cp_ = _native.edge_cam_pbwd_part_shape(pc.n_items)
     pbp = torch.empty(rp, cp_, device=dev)
@@ -165,10 +159,8 @@ def point_bench(run, rnd, n, dev):
     ra, ca = _native.point_hub_part_shape(n, 0, True)
     pc_, pa_ = torch.empty(rc, cc, device=dev), torch.empty(ra, ca, device=dev)
     dp = torch.empty(n, 64, device=dev)
-    run("point_hub_bwd_c", lambda: _native.point_hub_bwd_c(X, 1e-5, g64, b64, WC, bWC, WD, dXR, dsk, dp, pc_),
-        n * 640)
-    run("point_hub_bwd_ab", lambda: _native.point_hub_bwd_ab(X, 1e-5, g64, b64, WA, WB, dSA, dXL, dp, dp, pa_),
-        n * 1024)
+    run("point_hub_bwd", lambda: _native.point_hub_bwd(X, 1e-5, g64, b64, WA, WB, g64, b64, WC, bWC, WD, dSA, dXL, dXR,
+                                                        dsk, dp, pa_, pc_), n * 1280)
     del pb
 
 
