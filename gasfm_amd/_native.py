@@ -159,6 +159,9 @@ _SIGS = {
     "gasfm_esfm_seg_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _f32,
                                   _f32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gasfm_reproj_error_seg": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "gasfm_depth_stats_ws_doubles": (_i64, [_i64]),
+    "gasfm_depth_stats": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
+                                 _vp]),
     "gasfm_union_fill_scene": (_i32, [_vp, _vp, _vp]),
     "gasfm_fold_scene_rows_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp]),
     "gasfm_fold_scene_rows_bwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
@@ -1105,6 +1108,34 @@ def reproj_error(cam, pt, xy, P, X, err=None):
     st = lib().gasfm_reproj_error(_p(cam), _p(pt), _p(xy), E, _p(P), _p(X), n, _p(err), _p(part), _stream(X))
     check(st, "gasfm_reproj_error")
     return part
+
+
+def depth_stats(cam, pt, cam_ptr, pt_ptr, perm, P, X, margin, depth=None):
+    """gasfm_depth_stats: (cam_neg [m] int32, pt_neg [n] int32, stats [6] float64 = #negative edges,
+    #cameras / #points with an edge, sum, min, max of the edge depths); ``depth`` ([E] float32) is
+    filled when given.  ``perm`` None = the point CSR covers the edges in their own order."""
+    E, m, n = cam.shape[0], cam_ptr.shape[0] - 1, pt_ptr.shape[0] - 1
+    for t, name in ((cam, "cam"), (pt, "pt"), (cam_ptr, "cam_ptr"), (pt_ptr, "pt_ptr")):
+        _i32vec(t, name)
+    if perm is not None:
+        _i32vec(perm, "perm")
+    _req(P, "P", 12), _req(X, "pts3D", n)
+    if (X.dim() != 2 or X.shape[0] != 4 or P.dim() != 2 or P.shape[0] != m or pt.shape[0] != E
+            or (perm is not None and perm.shape[0] != E) or (depth is not None and depth.shape[0] != E)):
+        raise ValueError("depth_stats: expected P [m, 12], pts3D [4, n], cam_ptr [m + 1], pt_ptr [n + 1] and "
+                         "E-long cam / pt / perm / depth")
+    if depth is not None:
+        _req(depth, "depth")
+    dev = cam_ptr.device
+    cam_neg = torch.empty(m, dtype=torch.int32, device=dev)
+    pt_neg = torch.empty(n, dtype=torch.int32, device=dev)
+    stats = torch.empty(6, dtype=torch.float64, device=dev)
+    L = lib()
+    ws = torch.empty(int(L.gasfm_depth_stats_ws_doubles(E)), dtype=torch.float64, device=dev)
+    st = L.gasfm_depth_stats(_p(cam), _p(pt), E, _p(cam_ptr), m, _p(pt_ptr), _p(perm), n, _p(P), _p(X),
+                             float(margin), _p(depth), _p(cam_neg), _p(pt_neg), _p(ws), _p(stats), _stream(cam_ptr))
+    check(st, "gasfm_depth_stats")
+    return cam_neg, pt_neg, stats
 
 
 def _seg_args(eoff, S, name):

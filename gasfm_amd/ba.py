@@ -310,17 +310,40 @@ def normalized_observations(Ns, cidx, obs):
 
 
 class _Edges:
+    """The observations of a BA problem, camera-major: from the dense xs [m, n, 2] (the reference's
+    argument) or, with ``from_edges``, from a scene's own edge list (no dense array)."""
+
     def __init__(self, xs):
         vis = valid_points(xs)
         c, p = torch.nonzero(vis, as_tuple=True)  # camera-major (the reference's np.where order)
-        self.vis, self.cidx, self.pidx = vis, c, p
-        self.obs = xs[c, p].contiguous()
-        self.m, self.n = xs.shape[0], xs.shape[1]
-        cnt = torch.bincount(p, minlength=self.n)
-        self.pt_ptr = torch.zeros(self.n + 1, dtype=torch.int32, device=xs.device)
+        self._vis = vis
+        self._fill(c, p, xs[c, p].contiguous(), xs.shape[0], xs.shape[1])
+
+    @classmethod
+    def from_edges(cls, cidx, pidx, obs, m, n):
+        """Edges (cidx, pidx) camera-major with pixel observations obs [E, 2] of an m x n scene: the
+        network's edges are get_M_valid_points already, so nothing is filtered."""
+        ed = cls.__new__(cls)
+        ed._vis = None
+        ed._fill(cidx.to(torch.int64), pidx.to(torch.int64), obs.to(F64).contiguous(), int(m), int(n))
+        return ed
+
+    def _fill(self, c, p, obs, m, n):
+        self.cidx, self.pidx, self.obs, self.m, self.n = c, p, obs, m, n
+        cnt = torch.bincount(p, minlength=n)
+        self.pt_ptr = torch.zeros(n + 1, dtype=torch.int32, device=obs.device)
         self.pt_ptr[1:] = torch.cumsum(cnt, 0).to(torch.int32)
         self.perm = torch.argsort(p, stable=True).to(torch.int32).contiguous()
         self.c32 = c.to(torch.int32).contiguous()
+
+    @property
+    def vis(self):
+        """Dense [m, n] visibility mask (built on first use when the edges came as a list)."""
+        if self._vis is None:
+            v = torch.zeros((self.m, self.n), dtype=torch.bool, device=self.obs.device)
+            v[self.cidx, self.pidx] = True
+            self._vis = v
+        return self._vis
 
     def repro(self, Ps, Xs):
         """nanmean of reprojection_error_with_points (geo_utils.py:371-391) over the visible entries."""
@@ -380,17 +403,27 @@ def _out(res, numpy_out):
     return {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in res.items()}
 
 
+def _problem_device(xs, edges, device):
+    if device is not None:
+        return device
+    if edges is not None:
+        return edges.obs.device
+    return xs.device if torch.is_tensor(xs) and xs.is_cuda else torch.device("cuda", 0)
+
+
 def euc_ba(xs, Rs, ts, Ks, Xs_our=None, Ps=None, Ns=None, repeat=True, triangulation=False, return_repro=True,
-           print_out=True, device=None, **solver):
+           print_out=True, device=None, edges=None, **solver):
     """ba_functions.euc_ba (code/utils/ba_functions.py:6-72) on the GPU.  Same arguments and
     results (numpy in -> numpy out; CUDA tensors in -> tensors out): Rs, ts, Ps, Xs [n, 4] and,
-    with return_repro, repro_before / _middle / _middle_triangulated / _after."""
-    numpy_out = not torch.is_tensor(xs)
-    dev = device or (xs.device if torch.is_tensor(xs) and xs.is_cuda else torch.device("cuda", 0))
-    xs, Rs, ts, Ks = (_as_dev(a, dev) for a in (xs, Rs, ts, Ks))
+    with return_repro, repro_before / _middle / _middle_triangulated / _after.  ``edges``
+    (_Edges.from_edges) supplies the observations instead of the dense xs, which may then be None;
+    the output kind follows Rs."""
+    numpy_out = not torch.is_tensor(xs if edges is None else Rs)
+    dev = _problem_device(xs, edges, device)
+    xs, Rs, ts, Ks = (_as_dev(a, dev) for a in (None if edges is not None else xs, Rs, ts, Ks))
     Ps, Ns, Xs_our = _as_dev(Ps, dev), _as_dev(Ns, dev), _as_dev(Xs_our, dev)
     res = {}
-    ed = _Edges(xs)
+    ed = edges if edges is not None else _Edges(xs)
     if Ps is None:
         Ps = camera_matrices(Rs, ts, Ks)
     if triangulation:
@@ -430,16 +463,17 @@ def run_projective(Ps, Xs, ed, print_out=False, tag="ba", **kw):
 
 
 def proj_ba(Ps, xs, Xs_our=None, Ns=None, repeat=True, triangulation=False, return_repro=True, normalize_in_tri=True,
-            print_out=True, device=None, **solver):
+            print_out=True, device=None, edges=None, **solver):
     """ba_functions.proj_ba (code/utils/ba_functions.py:75-137) on the GPU; Ns is required when
-    triangulating with normalisation (the reference then derives it from the points otherwise)."""
-    numpy_out = not torch.is_tensor(xs)
-    dev = device or (xs.device if torch.is_tensor(xs) and xs.is_cuda else torch.device("cuda", 0))
-    xs, Ps, Ns, Xs_our = (_as_dev(a, dev) for a in (xs, Ps, Ns, Xs_our))
+    triangulating with normalisation (the reference then derives it from the points otherwise).
+    ``edges``: as in euc_ba (the output kind then follows Ps)."""
+    numpy_out = not torch.is_tensor(xs if edges is None else Ps)
+    dev = _problem_device(xs, edges, device)
+    xs, Ps, Ns, Xs_our = (_as_dev(a, dev) for a in (None if edges is not None else xs, Ps, Ns, Xs_our))
     if (triangulation or repeat) and normalize_in_tri and Ns is None:
         raise ValueError("proj_ba: pass Ns (normalisation matrices) for the normalised triangulation")
     res = {}
-    ed = _Edges(xs)
+    ed = edges if edges is not None else _Edges(xs)
     eye = torch.eye(3, dtype=F64, device=dev).expand(Ps.shape[0], 3, 3)
     Nt = Ns if normalize_in_tri else eye
     Xs = ed.dlt(Ps, Nt) if triangulation else Xs_our

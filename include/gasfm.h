@@ -798,6 +798,24 @@ int gasfm_gatt_merge_unpack(int32_t nprob, const gasfm_gatt_prob* probs, int32_t
  * operands of np.nanmean (finish with gasfm_colsum). */
 int gasfm_reproj_error(const int32_t* cam, const int32_t* pt, const float* xy, int64_t E, const float* P,
                        const float* pts3D, int64_t n, float* err, float* part, void* stream);
+/* Depth statistics of compute_errors (code/evaluation.py:351-363) over the E visibility edges
+ * (eval_metrics.hip) instead of the dense pts2D = Ps @ pflat(pts3D) [m, 3, n]:
+ * depth_e = P[c, 8:12] . (pts3D[:, p] / pts3D[3, p]), P = Ps_pix [m x 12], pts3D [4 x n];
+ * neg_e = !(depth_e >= margin), so a NaN depth is negative like the reference's `>=`.
+ * cam / pt [E] cam-major; cam_ptr [m + 1] the camera CSR over them; pt_ptr [n + 1] the point CSR
+ * over perm [E] (edge ids in point order; NULL = identity).  Every index must be in range.
+ * Outputs: depth [E] (optional, NULL skips it); cam_neg [m] / pt_neg [n] = 1 where any edge of the
+ * segment is negative, 0 otherwise (0 for an empty segment); stats [6] doubles = (#negative edges,
+ * #cameras with an edge, #points with an edge, sum, min, max of the depths).  The counts are
+ * reduced as integers, the sum in fp64 in a fixed order; sum, min and max propagate NaN
+ * (ndarray.mean / min / max).  Bitwise reproducible; no atomics.  ws: gasfm_depth_stats_ws_doubles(E)
+ * doubles.  E == 0: zero flags and counts, NaN sum / min / max; only stats, cam_neg (m > 0) and
+ * pt_neg (n > 0) are touched and every other pointer may be NULL. */
+int64_t gasfm_depth_stats_ws_doubles(int64_t E);
+int gasfm_depth_stats(const int32_t* cam, const int32_t* pt, int64_t E, const int32_t* cam_ptr, int32_t m,
+                      const int32_t* pt_ptr, const int32_t* perm, int64_t n, const float* P, const float* pts3D,
+                      float margin, float* depth, int32_t* cam_neg, int32_t* pt_neg, double* ws, double* stats,
+                      void* stream);
 /* ---- Adam over all parameter tensors in one launch (adam.hip; gasfm_amd/optim.py) ----
  * torch.optim.Adam's update (amsgrad off, maximize off; torch/optim/adam.py) for every tensor of
  * the table at optimizer step `step` (>= 1): g' = g + weight_decay p, m += (1 - beta1)(g' - m),
