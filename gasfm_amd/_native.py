@@ -69,6 +69,14 @@ _SIGS = {
     "gasfm_edge_prologue_bwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _f32, _vp,
                                        _vp, _vp, _i64, _vp]),
     "gasfm_segment_rowsum": (_i32, [_vp, _i32, _vp, _vp, _i64, _f32, _vp, _vp, _vp]),
+    "gasfm_sos_width_ok": (_i32, [_i32, _i32]),
+    "gasfm_sos_row_tile": (_i32, [_i32]),
+    "gasfm_sos_segment_sum": (_i32, [_vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "gasfm_sos_edge_fwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp,
+                                  _vp]),
+    "gasfm_sos_edge_dx": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gasfm_sos_dw_splits": (_i32, [_i64, _i32, _i32]),
+    "gasfm_sos_edge_dw": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
     "gasfm_colsum_counters": (_i32, [_i32]),
     "gasfm_colsum_multi": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gasfm_colsum_multi_counters": (_i32, [_i32, _vp]),
@@ -243,6 +251,7 @@ KERNELS = {
     "attn_fwd_grp": 0, "attn_fwd_glds": 1, "attn_fwd_vec": 2, "attn_fwd_generic": 3, "attn_fwd_lanes": 4,
     "attn_bwd_glds": 5, "attn_bwd_vec": 6, "attn_bwd_generic": 7, "attn_bwd_lanes": 8,
     "attn_combine_vec": 9, "attn_combine_generic": 10, "seam_reg": 13, "attn_fwd_grp_s2": 14, "attn_fwd_grp_s4": 15,
+    "sos_segsum": 16, "sos_edge_fwd": 17, "sos_edge_dx": 18, "sos_edge_dw": 19,
 }
 TUNING = {"attn_grp_rows": 0, "attn_grp_min_fill": 1, "attn_glds": 2, "attn_wave_cap": 3, "attn_grp_split": 4}
 
@@ -705,6 +714,102 @@ def segment_rowsum(items, n_items, perm, X, scale, out, part):
     st = lib().gasfm_segment_rowsum(_p(items), n_items, _p(perm), _p(X), X.stride(0), scale, _p(out), _p(part),
                                     _stream(X))
     check(st, "gasfm_segment_rowsum")
+
+
+# ---------------------------------------------------------------- set-of-set layer kernels
+def sos_width_ok(d_in, d_out):
+    return bool(lib().gasfm_sos_width_ok(int(d_in), int(d_out)))
+
+
+def sos_row_tile(n_cols):
+    return int(lib().gasfm_sos_row_tile(int(n_cols)))
+
+
+def sos_segment_sum(plan, X, scale=1.0, mean=False, mask=None):
+    """[num_targets, D] sums (means) of the rows of X over the plan's segments, optionally masked by
+    mask > 0; split items go through partial rows and the plan's ordered combines."""
+    _req(X, "sos_segment_sum X")
+    D = X.shape[1]
+    out = torch.zeros((plan.num_targets, D), dtype=torch.float32, device=X.device)
+    if plan.n_items == 0 or X.shape[0] == 0:
+        return out
+    if mask is not None:
+        _req(mask, "sos_segment_sum mask", D)
+    part = torch.empty((plan.n_part_rows, D), dtype=torch.float32, device=X.device) if plan.n_part_rows else None
+    st = lib().gasfm_sos_segment_sum(_p(plan.items), plan.n_items, _p(plan.perm), _p(X), X.stride(0), _p(mask),
+                                     0 if mask is None else mask.stride(0), D, float(scale),
+                                     _p(plan.seg_ptr) if mean else None, _p(out), _p(part), _stream(X))
+    check(st, "gasfm_sos_segment_sum")
+    if part is not None:
+        if plan.n_l1:
+            attn_bwd_combine(plan.combine_l1, plan.n_l1, D, part, part)
+        if plan.n_combine:
+            attn_bwd_combine(plan.combine, plan.n_combine, D, part, out)
+    return out
+
+
+def sos_edge_fwd(X, W, cam, pt, S, V, cmean, R, relu, out=None):
+    _req(X, "sos_edge_fwd X")
+    E, d_in = X.shape
+    d_out = W.shape[0]
+    for t, name, cols in ((W, "W", d_in), (S, "S", d_out), (V, "V", d_out)):
+        _req(t, "sos_edge_fwd " + name, cols)
+    Y = torch.empty((E, d_out), dtype=torch.float32, device=X.device) if out is None else out
+    _req(Y, "sos_edge_fwd out", d_out)
+    if Y.shape[0] != E:
+        raise ValueError(f"sos_edge_fwd out: {Y.shape[0]} rows, expected {E}")
+    if E == 0:
+        return Y
+    if cam.shape[0] != E or pt.shape[0] != E or cam.dtype != torch.int32 or pt.dtype != torch.int32:
+        raise ValueError("sos_edge_fwd: cam / pt must be int32 [E]")
+    if cmean is not None:
+        _req(cmean, "sos_edge_fwd cmean", d_out)
+    if R is not None:
+        _req(R, "sos_edge_fwd R", d_out)
+    st = lib().gasfm_sos_edge_fwd(_p(X), X.stride(0), _p(W), E, d_in, d_out, _p(cam), _p(pt), _p(S), _p(V),
+                                  _p(cmean), _p(R), 0 if R is None else R.stride(0), int(bool(relu)), _p(Y),
+                                  _stream(X))
+    check(st, "gasfm_sos_edge_fwd")
+    return Y
+
+
+def sos_edge_dx(dY, Ym, W, cam, pt, Ac, Bp, E, d_in, out=None):
+    """dX [E, d_in]; dY None: the gathered rows Ac[cam] + Bp[pt] alone."""
+    dev = cam.device
+    dX = torch.empty((E, d_in), dtype=torch.float32, device=dev) if out is None else out
+    _req(dX, "sos_edge_dx out", d_in)
+    if dX.shape[0] != E or cam.shape[0] != E or pt.shape[0] != E or (dY is not None and dY.shape[0] != E):
+        raise ValueError("sos_edge_dx: row counts differ")
+    if E == 0:
+        return dX
+    d_out = 0 if dY is None else dY.shape[1]
+    for t, name, cols in ((dY, "dY", None), (Ym, "Ym", d_out), (W, "W", d_in), (Ac, "Ac", d_in), (Bp, "Bp", d_in)):
+        if t is not None:
+            _req(t, "sos_edge_dx " + name, cols)
+    st = lib().gasfm_sos_edge_dx(_p(dY), _p(Ym), _p(W), E, d_in, d_out, _p(cam), _p(pt), _p(Ac), _p(Bp), _p(dX),
+                                 _stream(dX))
+    check(st, "gasfm_sos_edge_dx")
+    return dX
+
+
+def sos_edge_dw(dY, Ym, X):
+    """dW [d_out, d_in] = (mask . dY / 4)^T X: split-K partial matrices, then the ordered colsum."""
+    _req(dY, "sos_edge_dw dY")
+    _req(X, "sos_edge_dw X")
+    E, d_out = dY.shape
+    d_in = X.shape[1]
+    if E == 0:
+        return torch.zeros((d_out, d_in), dtype=torch.float32, device=dY.device)
+    if Ym is not None:
+        _req(Ym, "sos_edge_dw Ym", d_out)
+    L = lib()
+    splits = int(L.gasfm_sos_dw_splits(E, d_in, d_out))
+    part = torch.empty((splits, d_out * d_in), dtype=torch.float32, device=dY.device)
+    st = L.gasfm_sos_edge_dw(_p(dY), _p(Ym), _p(X), X.stride(0), E, d_in, d_out, splits, _p(part), _stream(dY))
+    check(st, "gasfm_sos_edge_dw")
+    if splits == 1:
+        return part.view(d_out, d_in)
+    return colsum(part).view(d_out, d_in)
 
 
 # ---------------------------------------------------------------- block 0 (2-wide) edge kernels

@@ -145,5 +145,7 @@ class SceneBatch:
 
 def forward_batch(net, datas, max_piece=None):
     """net(d) for every d in datas, as one forward over the union graph: list of prediction dicts."""
+    from .model import require_gasfm
+    require_gasfm(net, "forward_batch")
     batch = SceneBatch(datas, max_piece=max_piece)
     return batch.split(net(batch))

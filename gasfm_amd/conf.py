@@ -10,6 +10,7 @@ the reference's conf files use.  A real pyhocon ConfigTree works unchanged.
 Presets restate the ``model`` sections of
   confs/gasfm/learning_euc_rhaug-15-20_gasfm.conf:43-75  (12 blocks)
   confs/gasfm/optim_euc_gasfm.conf:9-38                  (9 blocks)
+  confs/dpesfm/learning_euc_rhaug-15-20_dpesfm.conf:43-65 (the SetOfSetNet baseline)
 """
 import copy
 import re
@@ -186,5 +187,26 @@ def small_conf(num_layers=2, **model_overrides):
     """Reduced widths for fast parity tests (SURVEY.md §8(c) fixture (ii))."""
     m = copy.deepcopy(_GASFM_MODEL)
     m.update({"num_layers": num_layers, "n_feat_view": 64, "n_feat_global": 128})
+    m.update(model_overrides)
+    return Conf({"dataset": {"calibrated": True}, "model": m})
+
+
+_DPESFM_MODEL = {
+    "type": "SetOfSet.SetOfSetNet",
+    "num_features": 256,
+    "proj_feat_normalization": True,
+    "add_skipconn_for_residual_blocks": False,
+    "num_blocks": 1,
+    "block_size": 3,
+    "pos_emb_n_freq": 0,
+    "depth_head": {"enabled": False, "n_feat": 128, "n_hidden_layers": 2},
+    "view_head": {"enabled": True, "n_hidden_layers": 2, "rot_representation": "quat"},
+    "scenepoint_head": {"enabled": True, "n_hidden_layers": 2},
+}
+
+
+def dpesfm_conf(**model_overrides):
+    """learning_euc_rhaug-15-20_dpesfm.conf model section (setofset.SetOfSetNet)."""
+    m = copy.deepcopy(_DPESFM_MODEL)
     m.update(model_overrides)
     return Conf({"dataset": {"calibrated": True}, "model": m})

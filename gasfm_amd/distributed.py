@@ -699,6 +699,8 @@ class ShardedGraphAttnSfMNet(torch.nn.Module):
         """cameras: the scenes come from shard_scene(..., cameras=True) (view rows sharded too):
         every parameter outside the global chain then carries a partial gradient."""
         super().__init__()
+        from .model import require_gasfm
+        require_gasfm(net, "ShardedGraphAttnSfMNet")
         self.net = net
         self.group = group
         self.cameras = cameras

@@ -934,12 +934,12 @@ torch.nn.modules.module.register_module_parameter_registration_hook(_bump_tree_v
 torch.nn.modules.module.register_module_module_registration_hook(_bump_tree_version)
 
 
-class GraphAttnSfMNet(Module):
-    """graph_attn_sfm.py:8-185 (BaseNet: baseNet.py:8-92)."""
+class BaseNet(Module):
+    """baseNet.py:8-92: the output format of a conf and the decoding of the head outputs, shared by
+    GraphAttnSfMNet and setofset.SetOfSetNet."""
 
-    def __init__(self, conf, batchnorm=False):
+    def __init__(self, conf):
         super().__init__()
-        # BaseNet
         self.calibrated = conf.get_bool("dataset.calibrated")
         self.normalize_output = conf.get_string("model.view_head.normalize_output", default=None)
         self.rot_representation = conf.get_string("model.view_head.rot_representation", default="quat")
@@ -954,6 +954,62 @@ class GraphAttnSfMNet(Module):
             self.out_channels = 12
         else:
             raise ValueError("Illegal output format")
+
+    @staticmethod
+    def extract_scenepoint_outputs(n_out):
+        """[3, n] head output -> {"pts3D": [4, n]} (ones-padded)."""
+        return {"pts3D": torch.cat([n_out, torch.ones(1, n_out.shape[1], dtype=n_out.dtype, device=n_out.device)])}
+
+    def extract_view_outputs(self, x):
+        if not self.calibrated:
+            Ps = x.reshape(-1, 3, 4)
+            if self.normalize_output == "Chirality":
+                Ps = Ps * (torch.sign(Ps[:, 0:3, 0:3].det()) / Ps[:, 2, 0:3].norm(dim=1)).reshape(-1, 1, 1)
+            elif self.normalize_output == "Differentiable Chirality":
+                Ps = Ps * (self.soft_sign(Ps[:, 0:3, 0:3].det() * 10e3) / Ps[:, 2, 0:3].norm(dim=1)).reshape(-1, 1, 1)
+            elif self.normalize_output == "Frobenius":
+                Ps = Ps / Ps.norm(dim=(1, 2), p="fro", keepdim=True)
+            return {"Ps_norm": Ps}
+        if self.rot_representation == "6d":
+            R = rotation_6d_to_matrix(x[:, :6])
+        elif self.rot_representation == "svd":
+            R = project_to_rot(x[:, :9].reshape(-1, 3, 3))
+        elif x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == 7:
+            return {"Ps_norm": QuatPoseFn.apply(x)}
+        else:
+            R = quaternion_to_matrix(x[:, :4])
+        return {"Ps_norm": torch.cat((R, x[:, -3:].unsqueeze(-1)), dim=-1)}
+
+
+def require_gasfm(net, what):
+    """The batched, captured-trainer and sharded paths are built around GraphAttnSfMNet's blocks."""
+    if not isinstance(net, GraphAttnSfMNet):
+        raise TypeError(f"{what} supports GraphAttnSfMNet only, got {type(net).__name__}")
+
+
+def scene_edge_index(data, device):
+    """The EdgeIndex (int32 camera / point ids, the four plans) of a scene on device, cached on its
+    SparseMat; accepts the reference's SceneData and this package's (host- or device-built)."""
+    x = data.x
+    cache = x.__dict__.setdefault("_gasfm_edges", {})
+    key = (str(device), x.indices.data_ptr())
+    if key not in cache:
+        cache.clear()
+        idx = x.indices.to(device)
+        plans = scene_plans(data, device)
+        soc = getattr(data, "scene_of_cam", None)
+        if soc is not None:  # a SceneBatch (batch.py): one global row per scene
+            plans["_scene_of_cam"] = soc.to(device)
+        cache[key] = EdgeIndex(idx[0].to(torch.int32).contiguous(), idx[1].to(torch.int32).contiguous(),
+                               x.shape[0], x.shape[1], plans)
+    return cache[key]
+
+
+class GraphAttnSfMNet(BaseNet):
+    """graph_attn_sfm.py:8-185 (BaseNet: baseNet.py:8-92)."""
+
+    def __init__(self, conf, batchnorm=False):
+        super().__init__(conf)
         g = lambda k, **kw: conf.get_int("model." + k, **kw)
         num_layers, n_heads = g("num_layers"), g("n_heads")
         n_feat_proj, n_feat_sp = g("n_feat_proj"), g("n_feat_scenepoint")
@@ -1040,19 +1096,7 @@ class GraphAttnSfMNet(Module):
 
     # ------------------------------------------------------------------ forward
     def edge_index_for(self, data, device):
-        x = data.x
-        cache = x.__dict__.setdefault("_gasfm_edges", {})
-        key = (str(device), x.indices.data_ptr())
-        if key not in cache:
-            cache.clear()
-            idx = x.indices.to(device)
-            plans = scene_plans(data, device)
-            soc = getattr(data, "scene_of_cam", None)
-            if soc is not None:  # a SceneBatch (batch.py): one global row per scene
-                plans["_scene_of_cam"] = soc.to(device)
-            cache[key] = EdgeIndex(idx[0].to(torch.int32).contiguous(), idx[1].to(torch.int32).contiguous(),
-                                   x.shape[0], x.shape[1], plans)
-        return cache[key]
+        return scene_edge_index(data, device)
 
     def forward_features(self, values, edges):
         """Block stack + final update on raw tensors; returns (P, pts, view) after the final update."""
@@ -1160,26 +1204,6 @@ class GraphAttnSfMNet(Module):
             n_out = dense.sequential(self.scenepoint_head, F.relu(pts)).T
             pred["pts3D"] = torch.cat([n_out, torch.ones(1, n_out.shape[1], dtype=n_out.dtype, device=device)])
         return pred
-
-    def extract_view_outputs(self, x):
-        if not self.calibrated:
-            Ps = x.reshape(-1, 3, 4)
-            if self.normalize_output == "Chirality":
-                Ps = Ps * (torch.sign(Ps[:, 0:3, 0:3].det()) / Ps[:, 2, 0:3].norm(dim=1)).reshape(-1, 1, 1)
-            elif self.normalize_output == "Differentiable Chirality":
-                Ps = Ps * (self.soft_sign(Ps[:, 0:3, 0:3].det() * 10e3) / Ps[:, 2, 0:3].norm(dim=1)).reshape(-1, 1, 1)
-            elif self.normalize_output == "Frobenius":
-                Ps = Ps / Ps.norm(dim=(1, 2), p="fro", keepdim=True)
-            return {"Ps_norm": Ps}
-        if self.rot_representation == "6d":
-            R = rotation_6d_to_matrix(x[:, :6])
-        elif self.rot_representation == "svd":
-            R = project_to_rot(x[:, :9].reshape(-1, 3, 3))
-        elif x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == 7:
-            return {"Ps_norm": QuatPoseFn.apply(x)}
-        else:
-            R = quaternion_to_matrix(x[:, :4])
-        return {"Ps_norm": torch.cat((R, x[:, -3:].unsqueeze(-1)), dim=-1)}
 
 
 class QuatPoseFn(torch.autograd.Function):

@@ -1,0 +1,320 @@
+"""``SetOfSetNet`` (the DPESFM baseline) for MI355X: same constructor, forward and state_dict as the
+reference's models/SetOfSet.py + models/layers.py:87-147, 959-984.
+
+One ``SetOfSetLayer(d_in, d_out)`` on the [E, d_in] edge features X of a scene is
+
+    mp[p], mc[c], mg = means of X over the edges of point p / of camera c / over all E edges
+    S = lin_scenepoint(mp), V = lin_view(mc), g = lin_global(mg)
+    Y[e] = (lin_proj(X[e]) + S[pt[e]] + V[cam[e]] + g) / 4
+
+The reference builds a torch sparse tensor and ``.coalesce()``s it in every layer; on the
+camera-major edge order of M2sparse that is the identity, so the layers here work on the edge rows
+directly with the scene's camera / point plans (attention.AttnPlan).
+
+Two paths, one module tree:
+  * composite: plain torch ops (index_add segment sums), any device, dtype and width: the CPU
+    path, the tests' fp64 oracle and tools/setofset_bench.py's baseline;
+  * fused (fp32 CUDA tensors, d_in == 2 or a multiple of 32 up to 256, d_out a multiple of 32 up
+    to 256): csrc/setofset.hip through ``SetOfSetLayerFn``.  The layer's forward is two segment-mean
+    launches (X read twice), node-sized linears and ONE edge kernel whose epilogue gathers S and
+    V (+ b + g folded into V), centres, adds the skip and applies the ReLU.  The centring vector is
+    not a pass over [E, d_out]: mean_e Y = (mg W^T + (sum_p deg_p S[p] + sum_c deg_c V'[c]) / E) / 4,
+    accumulated in fp64 from node-sized quantities.  The backward saves X and the layer's own
+    output (the next layer's X; its sign is the ReLU mask) and nothing else of size [E, d].
+"""
+import torch
+import torch.nn.functional as F
+from torch.nn import Linear, Module, ModuleList
+
+from . import _native, dense
+from .model import BaseNet, EmbeddingLayer, ProjLayer, get_linear_layers, scene_edge_index
+
+
+# ------------------------------------------------------------------ scene-side quantities
+class _Degrees:
+    """Per-point / per-camera edge counts of a scene (float32 and float64), cached on its EdgeIndex."""
+
+    def __init__(self, edges):
+        pp, pc = edges.plans["proj2scenepoint"], edges.plans["proj2view"]
+        self.E = int(edges.cam.shape[0])
+        for name, plan in (("p", pp), ("c", pc)):
+            deg = (plan.seg_ptr[1:] - plan.seg_ptr[:-1]).to(torch.float64)
+            setattr(self, "deg" + name, deg)
+            setattr(self, "inv" + name, torch.where(deg > 0, 1.0 / deg.clamp(min=1.0), torch.zeros_like(deg)))
+
+
+def _degrees(edges):
+    d = edges.__dict__.get("_sos_degrees")
+    if d is None:
+        d = edges.__dict__["_sos_degrees"] = _Degrees(edges)
+    return d
+
+
+def _composite_means(X, edges):
+    """(mp [n, d], mc [m, d], mg [1, d]) with index_add segment sums; empty segments give zero rows."""
+    cam, pt = edges.cam.long(), edges.pt.long()
+    E = X.shape[0]
+    ones = torch.ones(E, dtype=X.dtype, device=X.device)
+    degp = torch.zeros(edges.n, dtype=X.dtype, device=X.device).index_add(0, pt, ones).clamp(min=1)
+    degc = torch.zeros(edges.m, dtype=X.dtype, device=X.device).index_add(0, cam, ones).clamp(min=1)
+    mp = torch.zeros((edges.n, X.shape[1]), dtype=X.dtype, device=X.device).index_add(0, pt, X) / degp[:, None]
+    mc = torch.zeros((edges.m, X.shape[1]), dtype=X.dtype, device=X.device).index_add(0, cam, X) / degc[:, None]
+    mg = X.sum(0, keepdim=True) / max(E, 1)
+    return mp, mc, mg
+
+
+def fusable(X, d_in, d_out, edges):
+    """The fused kernels take this layer: fp32 CUDA rows of a covered width over plain plans."""
+    if not (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.shape[1] == d_in):
+        return False
+    pp, pc = edges.plans["proj2scenepoint"], edges.plans["proj2view"]
+    if pp.all_partial or pc.all_partial or "_scene_of_cam" in edges.plans or "_shard" in edges.plans:
+        return False
+    if pc.perm is not None or (pp.perm is not None and pp.perm.dtype != torch.int32):
+        return False
+    return _native.sos_width_ok(d_in, d_out)
+
+
+def segment_means(X, edges):
+    """Fused per-point and per-camera means of X ([n, d], [m, d]); X is read once per direction."""
+    return (_native.sos_segment_sum(edges.plans["proj2scenepoint"], X, mean=True),
+            _native.sos_segment_sum(edges.plans["proj2view"], X, mean=True))
+
+
+class SegmentMeansFn(torch.autograd.Function):
+    """(mp, mc) of X for the final global update; the backward is the gather-only edge kernel."""
+
+    @staticmethod
+    def forward(ctx, X, edges):
+        X = X.contiguous()
+        ctx.edges = edges
+        ctx.shape = X.shape
+        return segment_means(X, edges)
+
+    @staticmethod
+    def backward(ctx, dmp, dmc):
+        edges = ctx.edges
+        dg = _degrees(edges)
+        E, d = ctx.shape
+        Bp = (dmp.double() * dg.invp[:, None]).float().contiguous()
+        Ac = (dmc.double() * dg.invc[:, None]).float().contiguous()
+        return _native.sos_edge_dx(None, None, None, edges.cam, edges.pt, Ac, Bp, E, d), None
+
+
+class SetOfSetLayerFn(torch.autograd.Function):
+    """One SetOfSetLayer with what follows it in the block (centring, skip add, ReLU) fused."""
+
+    @staticmethod
+    def forward(ctx, X, Wp, bp, Wsp, bsp, Wv, bv, Wg, bg, R, edges, center, relu):
+        X = X.contiguous()
+        dg = _degrees(edges)
+        E = max(dg.E, 1)
+        mp, mc = segment_means(X, edges)
+        mg = (dg.degc @ mc.double()) / E                       # [d_in], fp64, fixed order (camera rows)
+        S = torch.addmm(bsp, mp, Wsp.t())
+        g = (mg.float() @ Wg.t() + bg) + bp                    # the global row and lin_proj's bias
+        Vb = torch.addmm(bv + g, mc, Wv.t())                   # V' = V + b + g: one gathered row per edge
+        cm = None
+        if center:
+            cm = (0.25 * (Wp.double() @ mg + (dg.degp @ S.double() + dg.degc @ Vb.double()) / E)).float()
+        Rc = None if R is None else R.contiguous()
+        Y = _native.sos_edge_fwd(X, Wp.contiguous(), edges.cam, edges.pt, S, Vb, cm, Rc, relu)
+        ctx.save_for_backward(X, Y if relu else None, Wp, Wsp, Wv, Wg, mp, mc, mg)
+        ctx.edges, ctx.center, ctx.has_R = edges, center, R is not None
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        X, Ym, Wp, Wsp, Wv, Wg, mp, mc, mg = ctx.saved_tensors
+        edges, dg = ctx.edges, _degrees(ctx.edges)
+        E = max(dg.E, 1)
+        dY = dY.contiguous()
+        pp, pc = edges.plans["proj2scenepoint"], edges.plans["proj2view"]
+        # dT = mask . dY / 4: its segment sums; node-sized from here on.  Column sums over the node
+        # rows go through the ordered colsum kernel (torch's reductions did not replay bitwise
+        # from a captured graph), elementwise work in fp64
+        dS32 = _native.sos_segment_sum(pp, dY, 0.25, mask=Ym)
+        dV32 = _native.sos_segment_sum(pc, dY, 0.25, mask=Ym)
+        dWp_extra = dmg = None
+        if ctx.center:
+            # cmean's gradient is -sum_e mask . dY; u = that / 4 through cmean's node-sized inputs
+            u = -_native.colsum(dV32).double()
+            dS32 = (dS32.double() + (dg.degp / E)[:, None] * u).float()
+            dV32 = (dV32.double() + (dg.degc / E)[:, None] * u).float()
+            dWp_extra = torch.outer(u, mg)
+            dmg = u @ Wp.double()
+        dgrow32 = _native.colsum(dV32)                         # db of lin_proj == the global row's gradient
+        dgrow = dgrow32.double()
+        dWsp, dbsp = dS32.t() @ mp, _native.colsum(dS32)
+        dWv, dbv = dV32.t() @ mc, dgrow32.clone()       # one tensor per parameter: .grad adopts it
+        dWg, dbg = torch.outer(dgrow, mg).float(), dgrow32.clone()
+        dmg_t = dgrow @ Wg.double()
+        dmg = dmg_t if dmg is None else dmg + dmg_t
+        dX = None
+        if ctx.needs_input_grad[0]:
+            dmp = dS32 @ Wsp
+            dmc = (dV32 @ Wv).double() + (dg.degc / E)[:, None] * dmg  # mg = sum_c deg_c mc[c] / E
+            Bp = (dmp.double() * dg.invp[:, None]).float()
+            Ac = (dmc * dg.invc[:, None]).float()
+            dX = _native.sos_edge_dx(dY, Ym, Wp.contiguous(), edges.cam, edges.pt, Ac, Bp, X.shape[0], X.shape[1])
+        dWp = _native.sos_edge_dw(dY, Ym, X)
+        if dWp_extra is not None:
+            dWp = (dWp.double() + dWp_extra).float()
+        dR = None
+        if ctx.has_R and ctx.needs_input_grad[9]:
+            dR = dY if Ym is None else dY * (Ym > 0)
+        return dX, dWp, dgrow32, dWsp, dbsp, dWv, dbv, dWg, dbg, dR, None, None, None
+
+
+# ------------------------------------------------------------------ modules (reference key names)
+class SetOfSetGlobalFeatureUpdate(Module):
+    """layers.py:100-126."""
+
+    def __init__(self, d_in, d_out, output_global=True):
+        super().__init__()
+        self.lin_scenepoint = Linear(d_in, d_out)
+        self.lin_view = Linear(d_in, d_out)
+        self.output_global = output_global
+        if output_global:
+            self.lin_global = Linear(d_in, d_out)
+
+    def forward(self, X, edges):
+        """The final update (output_global False) on raw tensors: (S [n, d_out], V [m, d_out])."""
+        if fusable(X, X.shape[1], 32, edges):
+            mp, mc = SegmentMeansFn.apply(X, edges)
+        else:
+            mp, mc, _ = _composite_means(X, edges)
+        return dense.linear(mp, self.lin_scenepoint), dense.linear(mc, self.lin_view)
+
+
+class SetOfSetProjectionFeatureUpdate(Module):
+    """layers.py:129-147."""
+
+    def __init__(self, d_in, d_out):
+        super().__init__()
+        self.lin_proj = Linear(d_in, d_out)
+
+
+class SetOfSetLayer(Module):
+    """layers.py:87-97, with the block's centring / skip add / ReLU that follow it."""
+
+    def __init__(self, d_in, d_out):
+        super().__init__()
+        self.d_in, self.d_out = d_in, d_out
+        self.global_feature_update = SetOfSetGlobalFeatureUpdate(d_in, d_out)
+        self.projection_feature_update = SetOfSetProjectionFeatureUpdate(d_in, d_out)
+
+    def forward(self, X, edges, center=False, relu=False, residual=None, composite=False):
+        gfu, lp = self.global_feature_update, self.projection_feature_update.lin_proj
+        if not composite and fusable(X, self.d_in, self.d_out, edges):
+            return SetOfSetLayerFn.apply(X, lp.weight, lp.bias, gfu.lin_scenepoint.weight, gfu.lin_scenepoint.bias,
+                                         gfu.lin_view.weight, gfu.lin_view.bias, gfu.lin_global.weight,
+                                         gfu.lin_global.bias, residual, edges, center, relu)
+        mp, mc, mg = _composite_means(X, edges)
+        S, V, g = gfu.lin_scenepoint(mp), gfu.lin_view(mc), gfu.lin_global(mg)
+        Y = (lp(X) + S[edges.pt.long()] + V[edges.cam.long()] + g) / 4
+        if center:
+            Y = Y - Y.mean(dim=0, keepdim=True) if Y.shape[0] else Y
+        if residual is not None:
+            Y = residual + Y
+        return F.relu(Y) if relu else Y
+
+
+class SetOfSetBlock(Module):
+    """SetOfSet.py:7-46."""
+
+    def __init__(self, d_in, d_out, conf):
+        super().__init__()
+        self.block_size = conf.get_int("model.block_size")
+        self.proj_feat_normalization = conf.get_bool("model.proj_feat_normalization")
+        self.add_skipconn_for_residual_blocks = conf.get_bool("model.add_skipconn_for_residual_blocks")
+        self.layers = ModuleList([SetOfSetLayer(d_in, d_out)]
+                                 + [SetOfSetLayer(d_out, d_out) for _ in range(1, self.block_size)])
+        if self.add_skipconn_for_residual_blocks:
+            self.skip_projection = None if d_in == d_out else ProjLayer(d_in, d_out)
+
+    def forward(self, X, edges, composite=False):
+        skip = None
+        if self.add_skipconn_for_residual_blocks:
+            skip = X
+            if self.skip_projection is not None:
+                skip = dense.linear(X, self.skip_projection.lin_proj)
+                if self.proj_feat_normalization and skip.shape[0]:
+                    skip = skip - skip.mean(dim=0, keepdim=True)
+        xl = X
+        last = len(self.layers) - 1
+        for i, layer in enumerate(self.layers):
+            if i < last:
+                xl = layer(xl, edges, center=self.proj_feat_normalization, relu=True, composite=composite)
+            else:  # the skip add and the block's final ReLU in the last layer's epilogue
+                xl = layer(xl, edges, center=False, relu=True, residual=skip, composite=composite)
+        return xl
+
+
+class SetOfSetNet(BaseNet):
+    """SetOfSet.py:49-142."""
+
+    def __init__(self, conf, batchnorm=False):
+        super().__init__(conf)
+        num_blocks = conf.get_int("model.num_blocks")
+        num_feats = conf.get_int("model.num_features")
+        pos_emb_n_freq = conf.get_int("model.pos_emb_n_freq")
+        self.depth_head_enabled = conf.get_bool("model.depth_head.enabled", default=False)
+        self.view_head_enabled = conf.get_bool("model.view_head.enabled", default=False)
+        self.scenepoint_head_enabled = conf.get_bool("model.scenepoint_head.enabled", default=False)
+        self.batchnorm = batchnorm
+        n_feat_depth = conf.get_int("model.depth_head.n_feat") if self.depth_head_enabled else None
+        self.embed = EmbeddingLayer(pos_emb_n_freq, 2)  # raises for pos_emb_n_freq > 0
+        self.equivariant_blocks = ModuleList()
+        for i in range(num_blocks):
+            self.equivariant_blocks.append(SetOfSetBlock(
+                self.embed.d_out if i == 0 else num_feats,
+                n_feat_depth if self.depth_head_enabled and i == num_blocks - 1 else num_feats, conf))
+        if self.view_head_enabled or self.scenepoint_head_enabled:
+            if not self.view_head_enabled:
+                raise NotImplementedError("Final feature aggregation for only view features or scenepoint features "
+                                          "alone is not implemented.")
+            self.final_global_update = SetOfSetGlobalFeatureUpdate(num_feats, num_feats, output_global=False)
+        if self.batchnorm:
+            raise NotImplementedError()
+        if self.depth_head_enabled:
+            nh = conf.get_int("model.depth_head.n_hidden_layers")
+            self.depth_head = get_linear_layers((1 + nh) * [n_feat_depth] + [1], norm=False)
+        if self.view_head_enabled:
+            nh = conf.get_int("model.view_head.n_hidden_layers")
+            self.view_head = get_linear_layers((1 + nh) * [num_feats] + [self.out_channels], norm=False)
+        if self.scenepoint_head_enabled:
+            nh = conf.get_int("model.scenepoint_head.n_hidden_layers")
+            self.scenepoint_head = get_linear_layers((1 + nh) * [num_feats] + [3], norm=False)
+
+    # False: every layer on the fused kernels where they apply; True: the torch-op composite path
+    composite = False
+
+    def edge_index_for(self, data, device):
+        return scene_edge_index(data, device)
+
+    def forward(self, data):
+        values = data.x.values
+        edges = self.edge_index_for(data, values.device)
+        x = self.embed(values)
+        for blk in self.equivariant_blocks:
+            x = blk(x, edges, composite=self.composite)
+        pred = {}
+        if self.depth_head_enabled:
+            from .scene import SparseMat
+            sx = data.x
+            pred["depths"] = SparseMat(self.depth_head(x), sx.indices, sx.cam_per_pts, sx.pts_per_cam,
+                                       [sx.shape[0], sx.shape[1], 1])
+        if self.view_head_enabled or self.scenepoint_head_enabled:
+            if self.composite:
+                mp, mc, _ = _composite_means(x, edges)
+                fgu = self.final_global_update
+                n_in, m_in = fgu.lin_scenepoint(mp), fgu.lin_view(mc)
+            else:
+                n_in, m_in = self.final_global_update(x, edges)
+            n_in, m_in = F.relu(n_in), F.relu(m_in)
+        if self.view_head_enabled:
+            pred.update(self.extract_view_outputs(dense.sequential(self.view_head, m_in)))
+        if self.scenepoint_head_enabled:
+            pred.update(self.extract_scenepoint_outputs(dense.sequential(self.scenepoint_head, n_in).T))
+        return pred

@@ -51,7 +51,7 @@ from . import _native
 from .attention import DEFAULT_MAX_PIECE, AttnPlan
 from .batch import _scene_arrays
 from .graph_step import gc_paused
-from .model import EdgeIndex
+from .model import EdgeIndex, require_gasfm
 from .scene import MIN_N_POINTS_PER_VIEW, MIN_N_VIEWS_PER_POINT, AxialAggregationGraphWrapper, SparseMat
 
 PIECE = DEFAULT_MAX_PIECE  # camera pieces: ceil(deg / PIECE) per real camera, as the eager plans
@@ -545,6 +545,7 @@ class StaticTrainer:
 
     def __init__(self, net, lossf, warmup=2, optimizer=None, max_buckets=32):
         """max_buckets: the least recently used bucket (its graphs and buffers) is dropped beyond it."""
+        require_gasfm(net, "StaticTrainer")
         self.net, self.lossf = net, lossf
         self.max_buckets = max_buckets
         self.optimizer = optimizer

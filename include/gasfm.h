@@ -80,7 +80,11 @@ enum {
   GASFM_K_SEAM_REG = 13,         /* forward seam (blocks 1-11) */
   GASFM_K_ATTN_FWD_GRP_S2 = 14,  /* grouped items, 2 lane groups per item (also counted as _GRP) */
   GASFM_K_ATTN_FWD_GRP_S4 = 15,  /* grouped items, 4 lane groups per item (also counted as _GRP) */
-  GASFM_K_COUNT = 16
+  GASFM_K_SOS_SEGSUM = 16,       /* set-of-set: width-general segment sums */
+  GASFM_K_SOS_EDGE_FWD = 17,     /* set-of-set: fused edge update forward */
+  GASFM_K_SOS_EDGE_DX = 18,      /* set-of-set: edge update input gradient (+ the means' backward) */
+  GASFM_K_SOS_EDGE_DW = 19,      /* set-of-set: split-K weight gradient */
+  GASFM_K_COUNT = 20
 };
 
 /* Copies min(n, GASFM_K_COUNT) counters into out; returns GASFM_K_COUNT. */
@@ -377,6 +381,37 @@ int gasfm_edge_prologue_bwd(const float* dXL, int64_t ldX, const float* P, const
 int gasfm_segment_rowsum(const gasfm_work_item* items, int32_t n_items, const int32_t* perm,
                          const float* X, int64_t ldX, float scale, float* out, float* part,
                          void* stream);
+
+/* ---- set-of-set (DPESFM baseline) layers (models/layers.py:87-147; csrc/setofset.hip) ---- */
+
+/* Widths the fused kernels take: d_in == 2 or a multiple of 32 up to 256; d_out a multiple of 32
+ * up to 256. */
+int32_t gasfm_sos_width_ok(int32_t d_in, int32_t d_out);
+/* Rows per workgroup tile of the edge kernels for an output of n_cols columns. */
+int32_t gasfm_sos_row_tile(int32_t n_cols);
+/* Segment sums of any such width D over a plan's work items: complete items (slot < 0) write
+ * out[seg * D], split items part[slot * D] (merge with gasfm_gat_attn_bwd_combine, HC = D), both
+ * scaled by scale, and by 1 / deg(seg) when seg_ptr is given (segment means; an empty segment
+ * gives a zero row).  Ym (optional, same row indexing as X): rows are masked by Ym > 0. */
+int gasfm_sos_segment_sum(const gasfm_work_item* items, int32_t n_items, const int32_t* perm,
+                          const float* X, int64_t ldX, const float* Ym, int64_t ldY, int32_t D,
+                          float scale, const int32_t* seg_ptr, float* out, float* part, void* stream);
+/* Y[e] = act((X[e] W^T + S[pt[e]] + V[cam[e]]) / 4 - cmean + R[e]); W [d_out, d_in]; cmean
+ * [d_out] and R [E, ldR] optional; act = ReLU when relu != 0.  Y [E, d_out] contiguous. */
+int gasfm_sos_edge_fwd(const float* X, int64_t ldX, const float* W, int64_t E, int32_t d_in,
+                       int32_t d_out, const int32_t* cam, const int32_t* pt, const float* S,
+                       const float* V, const float* cmean, const float* R, int64_t ldR, int32_t relu,
+                       float* Y, void* stream);
+/* dX[e] = (mask . dY / 4)[e] W + Ac[cam[e]] + Bp[pt[e]]; mask = Ym > 0 (all ones when Ym is null);
+ * Ac [m, d_in], Bp [n, d_in] optional.  d_out == 0: the gathered rows alone. */
+int gasfm_sos_edge_dx(const float* dY, const float* Ym, const float* W, int64_t E, int32_t d_in,
+                      int32_t d_out, const int32_t* cam, const int32_t* pt, const float* Ac,
+                      const float* Bp, float* dX, void* stream);
+/* part[s] [d_out, d_in] = (mask . dY / 4)^T X over the s-th of `splits` ranges of the E rows;
+ * reduce the [splits, d_out * d_in] partial rows with gasfm_colsum. */
+int32_t gasfm_sos_dw_splits(int64_t E, int32_t d_in, int32_t d_out);
+int gasfm_sos_edge_dw(const float* dY, const float* Ym, const float* X, int64_t ldX, int64_t E,
+                      int32_t d_in, int32_t d_out, int32_t splits, float* part, void* stream);
 
 /* ---- block 0 per-edge body (2-wide embedded projections; layers.py:148-263 with F_in = 2) ---- */
 
