@@ -84,6 +84,7 @@ _SIGS = {
     "gasfm_colsum_tall_ok": (_i32, [_i32]),
     "gasfm_colsum_tall_ws_floats": (_i64, [_i64, _i32]),
     "gasfm_colsum_tall": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "gasfm_colsum_ranges": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp]),
     "gasfm_edge0_part_rows": (_i32, [_i32, _i64, _i32]),
     "gasfm_edge0_prologue_fwd": (_i32, [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
     "gasfm_edge0_prologue_fwd_rows": (_i32, [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
@@ -444,6 +445,34 @@ def colsum_tall(A, out=None):
     cnt = _counters(A.device, 1)
     st = L.gasfm_colsum_tall(_p(A), rows, cols, _p(ws), _p(out), _p(cnt), _stream(out))
     check(st, "gasfm_colsum_tall")
+    return out
+
+
+def colsum_ranges(A, row_ptr, w=None, out=None):
+    """[n_ranges, cols] fp64: out[s] = sum of w[r] * A[r] over rows row_ptr[s] <= r < row_ptr[s + 1]
+    of a 2-D fp32 CUDA tensor (row stride may exceed cols).  row_ptr: int32 device row pointers
+    within A's rows (not read here: no host synchronisation); w: fp64 [rows] or None.  One launch,
+    ordered fp64 sums (csrc/colsum_ranges.hip)."""
+    if not (A.is_cuda and A.dim() == 2 and A.dtype == torch.float32 and (A.shape[1] == 1 or A.stride(1) == 1)):
+        raise ValueError("colsum_ranges: A must be a 2-D fp32 CUDA tensor with unit column stride")
+    rows, cols = A.shape
+    if cols < 1:
+        raise ValueError("colsum_ranges: A has no columns")
+    if row_ptr.dtype != torch.int32 or row_ptr.dim() != 1 or row_ptr.numel() < 1 or not row_ptr.is_contiguous() \
+            or row_ptr.device != A.device:
+        raise ValueError("colsum_ranges: row_ptr must be a contiguous int32 vector on A's device")
+    n_ranges = row_ptr.numel() - 1
+    if w is not None and not (w.dtype == torch.float64 and w.dim() == 1 and w.numel() == rows and w.is_contiguous()
+                              and w.device == A.device):
+        raise ValueError("colsum_ranges: w must be a contiguous fp64 vector with one entry per row of A")
+    if out is None:
+        out = torch.empty((n_ranges, cols), dtype=torch.float64, device=A.device)
+    elif not (out.dtype == torch.float64 and tuple(out.shape) == (n_ranges, cols) and out.is_contiguous()
+              and out.device == A.device):
+        raise ValueError(f"colsum_ranges: out must be a contiguous fp64 [{n_ranges}, {cols}] tensor")
+    ld = max(A.stride(0), cols) if rows > 1 else cols
+    st = lib().gasfm_colsum_ranges(_p(A), ld, cols, _p(row_ptr), n_ranges, _p(w), _p(out), _stream(out))
+    check(st, "gasfm_colsum_ranges")
     return out
 
 

@@ -144,8 +144,16 @@ class SceneBatch:
 
 
 def forward_batch(net, datas, max_piece=None):
-    """net(d) for every d in datas, as one forward over the union graph: list of prediction dicts."""
+    """net(d) for every d in datas, as one forward over the union graph: list of prediction dicts.
+    net: a GraphAttnSfMNet, or a setofset.SetOfSetNet (its layers take the global mean, the global
+    row and the centring per scene from the union's row ranges).
+
+    An empty ``datas`` is refused as it was before SetOfSetNet was accepted, so callers that relied
+    on either error keep it: the GraphAttnSfMNet-only TypeError for any other net (the set-of-set
+    route is taken for a batch of at least one scene), SceneBatch's ValueError for GraphAttnSfMNet."""
     from .model import require_gasfm
-    require_gasfm(net, "forward_batch")
+    from .setofset import SetOfSetNet
+    if not (isinstance(net, SetOfSetNet) and len(datas) > 0):
+        require_gasfm(net, "forward_batch")
     batch = SceneBatch(datas, max_piece=max_piece)
     return batch.split(net(batch))

@@ -1000,6 +1000,9 @@ def scene_edge_index(data, device):
         soc = getattr(data, "scene_of_cam", None)
         if soc is not None:  # a SceneBatch (batch.py): one global row per scene
             plans["_scene_of_cam"] = soc.to(device)
+            off = tuple(getattr(data, k, None) for k in ("cam_off", "pt_off", "edge_off"))
+            if all(o is not None for o in off):  # the scenes' row ranges (host lists): setofset's per-scene means
+                plans["_scene_off"] = off
         cache[key] = EdgeIndex(idx[0].to(torch.int32).contiguous(), idx[1].to(torch.int32).contiguous(),
                                x.shape[0], x.shape[1], plans)
     return cache[key]

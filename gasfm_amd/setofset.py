@@ -21,6 +21,12 @@ Two paths, one module tree:
     not a pass over [E, d_out]: mean_e Y = (mg W^T + (sum_p deg_p S[p] + sum_c deg_c V'[c]) / E) / 4,
     accumulated in fp64 from node-sized quantities.  The backward saves X and the layer's own
     output (the next layer's X; its sign is the ReLU mask) and nothing else of size [E, d].
+
+A union of B scenes (batch.SceneBatch, ``batch.forward_batch``) runs on both paths with the global
+mean, the global row g and the centring vector taken per scene: the scenes' cameras, points and
+edges are contiguous row ranges, so these are [B, d] matrices of per-range column sums
+(csrc/colsum_ranges.hip on the fused path, index_add on the composite), gathered by the scene of
+each camera / edge.
 """
 import torch
 import torch.nn.functional as F
@@ -32,7 +38,10 @@ from .model import BaseNet, EmbeddingLayer, ProjLayer, get_linear_layers, scene_
 
 # ------------------------------------------------------------------ scene-side quantities
 class _Degrees:
-    """Per-point / per-camera edge counts of a scene (float32 and float64), cached on its EdgeIndex."""
+    """Per-point / per-camera edge counts of a scene (float32 and float64), cached on its EdgeIndex.
+    For a union of B scenes (B is not None) also the scenes' row ranges: int32 row pointers ptrc /
+    ptrp / ptre, the scene of every camera / point / edge row soc / sop / soe, Es = max(E_s, 1) and
+    deg / E_s per camera and point (wc, wp)."""
 
     def __init__(self, edges):
         pp, pc = edges.plans["proj2scenepoint"], edges.plans["proj2view"]
@@ -41,6 +50,29 @@ class _Degrees:
             deg = (plan.seg_ptr[1:] - plan.seg_ptr[:-1]).to(torch.float64)
             setattr(self, "deg" + name, deg)
             setattr(self, "inv" + name, torch.where(deg > 0, 1.0 / deg.clamp(min=1.0), torch.zeros_like(deg)))
+        # a union of B scenes (batch.SceneBatch): every scene's cameras, points and edges are a
+        # contiguous row range.  Built once from the batch's host lists; the layers read device
+        # tensors only, so a step over a fixed union captures
+        self.B = None
+        off = edges.plans.get("_scene_off")
+        if off is None:
+            if "_scene_of_cam" in edges.plans:
+                raise TypeError("SetOfSetNet: this union carries no per-scene row ranges (only batch.SceneBatch "
+                                "unions are supported)")
+            return
+        dev = edges.cam.device
+        self.B = len(off[0]) - 1
+        if any(len(o) != self.B + 1 for o in off):
+            raise ValueError("SetOfSetNet: the union's cam / pt / edge offsets differ in length")
+        ptrs = torch.tensor([list(o) for o in off], dtype=torch.int32, device=dev)           # one copy to the device
+        ar = torch.arange(self.B, device=dev)
+        for name, ptr, o in zip(("c", "p", "e"), ptrs, off):
+            setattr(self, "ptr" + name, ptr)                                                   # int32 row pointers
+            cnt = (ptr[1:] - ptr[:-1]).long()
+            setattr(self, "so" + name, torch.repeat_interleave(ar, cnt, output_size=o[-1]))   # scene of row
+        self.ptr_all_c = self.ptrc[::self.B].contiguous()                                      # [0, M]: all cameras
+        self.Es = (self.ptre[1:] - self.ptre[:-1]).clamp(min=1).double()                       # max(E_s, 1)
+        self.wc, self.wp = self.degc / self.Es[self.soc], self.degp / self.Es[self.sop]      # deg / E_s per node
 
 
 def _degrees(edges):
@@ -50,8 +82,22 @@ def _degrees(edges):
     return d
 
 
+def _union(edges):
+    """The _Degrees of a union of scenes (per-scene global mean and centring); None for one scene."""
+    if "_scene_of_cam" not in edges.plans:
+        return None
+    return _degrees(edges)
+
+
+def _scene_means(X, u):
+    """[B, d] means of the rows of X over each scene's edge rows (index_add; any dtype, any device)."""
+    tot = torch.zeros((u.B, X.shape[1]), dtype=X.dtype, device=X.device).index_add(0, u.soe, X)
+    return tot / u.Es.to(X.dtype)[:, None]
+
+
 def _composite_means(X, edges):
-    """(mp [n, d], mc [m, d], mg [1, d]) with index_add segment sums; empty segments give zero rows."""
+    """(mp [n, d], mc [m, d], mg [1, d]) with index_add segment sums; empty segments give zero rows.
+    For a union of B scenes mg is [B, d]: one mean per scene."""
     cam, pt = edges.cam.long(), edges.pt.long()
     E = X.shape[0]
     ones = torch.ones(E, dtype=X.dtype, device=X.device)
@@ -59,16 +105,30 @@ def _composite_means(X, edges):
     degc = torch.zeros(edges.m, dtype=X.dtype, device=X.device).index_add(0, cam, ones).clamp(min=1)
     mp = torch.zeros((edges.n, X.shape[1]), dtype=X.dtype, device=X.device).index_add(0, pt, X) / degp[:, None]
     mc = torch.zeros((edges.m, X.shape[1]), dtype=X.dtype, device=X.device).index_add(0, cam, X) / degc[:, None]
-    mg = X.sum(0, keepdim=True) / max(E, 1)
+    u = _union(edges)
+    mg = X.sum(0, keepdim=True) / max(E, 1) if u is None else _scene_means(X, u)
     return mp, mc, mg
 
 
+def _center_rows(Y, edges):
+    """Y minus its mean over the edge rows, per scene for a union (torch ops)."""
+    if not Y.shape[0]:
+        return Y
+    u = _union(edges)
+    if u is None:
+        return Y - Y.mean(dim=0, keepdim=True)
+    return Y - _scene_means(Y, u)[u.soe]
+
+
 def fusable(X, d_in, d_out, edges):
-    """The fused kernels take this layer: fp32 CUDA rows of a covered width over plain plans."""
+    """The fused kernels take this layer: fp32 CUDA rows of a covered width over plain plans (one
+    scene, or a batch.SceneBatch union with its per-scene row ranges)."""
     if not (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.shape[1] == d_in):
         return False
     pp, pc = edges.plans["proj2scenepoint"], edges.plans["proj2view"]
-    if pp.all_partial or pc.all_partial or "_scene_of_cam" in edges.plans or "_shard" in edges.plans:
+    if pp.all_partial or pc.all_partial or "_shard" in edges.plans:
+        return False
+    if "_scene_of_cam" in edges.plans and "_scene_off" not in edges.plans:
         return False
     if pc.perm is not None or (pp.perm is not None and pp.perm.dtype != torch.int32):
         return False
@@ -108,6 +168,9 @@ class SetOfSetLayerFn(torch.autograd.Function):
     def forward(ctx, X, Wp, bp, Wsp, bsp, Wv, bv, Wg, bg, R, edges, center, relu):
         X = X.contiguous()
         dg = _degrees(edges)
+        ctx.union = dg.B is not None
+        if ctx.union:
+            return SetOfSetLayerFn._forward_union(ctx, X, Wp, bp, Wsp, bsp, Wv, bv, Wg, bg, R, edges, center, relu, dg)
         E = max(dg.E, 1)
         mp, mc = segment_means(X, edges)
         mg = (dg.degc @ mc.double()) / E                       # [d_in], fp64, fixed order (camera rows)
@@ -124,7 +187,67 @@ class SetOfSetLayerFn(torch.autograd.Function):
         return Y
 
     @staticmethod
+    def _forward_union(ctx, X, Wp, bp, Wsp, bsp, Wv, bv, Wg, bg, R, edges, center, relu, dg):
+        """A union of B scenes: the global mean, the global row and the centring vector are one row
+        per scene ([B, .], fp64, from the ordered per-range column sums).  Every camera belongs to
+        one scene, so both the global row and the centring vector are folded into its gathered row
+        V'[c] and the edge kernel runs as for one scene, with no centring vector of its own."""
+        mp, mc = segment_means(X, edges)
+        inv_E = 1.0 / dg.Es[:, None]
+        MG = _native.colsum_ranges(mc, dg.ptrc, dg.degc) * inv_E             # [B, d_in]
+        S = torch.addmm(bsp, mp, Wsp.t())
+        G = (MG.float() @ Wg.t() + bg) + bp                                    # [B, d_out]
+        Vb = torch.addmm(bv, mc, Wv.t()) + G[dg.soc]
+        if center:  # 4 cm_s = Wp mg_s + (sum_p deg_p S[p] + sum_c deg_c V'[c]) / E_s; Y = (.. + V') / 4
+            cm4 = MG @ Wp.double().t() + (_native.colsum_ranges(S, dg.ptrp, dg.degp)
+                                          + _native.colsum_ranges(Vb, dg.ptrc, dg.degc)) * inv_E
+            Vb = (Vb.double() - cm4[dg.soc]).float()
+        Rc = None if R is None else R.contiguous()
+        Y = _native.sos_edge_fwd(X, Wp.contiguous(), edges.cam, edges.pt, S, Vb, None, Rc, relu)
+        ctx.save_for_backward(X, Y if relu else None, Wp, Wsp, Wv, Wg, mp, mc, MG)
+        ctx.edges, ctx.center, ctx.has_R = edges, center, R is not None
+        return Y
+
+    @staticmethod
+    def _backward_union(ctx, dY):
+        X, Ym, Wp, Wsp, Wv, Wg, mp, mc, MG = ctx.saved_tensors
+        edges, dg = ctx.edges, _degrees(ctx.edges)
+        dY = dY.contiguous()
+        pp, pc = edges.plans["proj2scenepoint"], edges.plans["proj2view"]
+        dS32 = _native.sos_segment_sum(pp, dY, 0.25, mask=Ym)
+        dV32 = _native.sos_segment_sum(pc, dY, 0.25, mask=Ym)
+        U = None
+        if ctx.center:  # u_s = -sum_{c in s} dV32[c]: the gradient of 4 cm_s, through its node-sized inputs
+            U = -_native.colsum_ranges(dV32, dg.ptrc)                          # [B, d_out]
+            dS32 = (dS32.double() + dg.wp[:, None] * U[dg.sop]).float()
+            dV32 = (dV32.double() + dg.wc[:, None] * U[dg.soc]).float()
+        DG = _native.colsum_ranges(dV32, dg.ptrc)                              # [B, d_out]: the global rows' gradient
+        dgrow32 = _native.colsum_ranges(dV32, dg.ptr_all_c)[0].float()         # sum_s DG[s]: the shared biases
+        dWsp, dbsp = dS32.t() @ mp, _native.colsum(dS32)
+        dWv, dbv = dV32.t() @ mc, dgrow32.clone()
+        dWg, dbg = (DG.t() @ MG).float(), dgrow32.clone()
+        dMG = DG @ Wg.double()
+        if U is not None:
+            dMG = dMG + U @ Wp.double()
+        dX = None
+        if ctx.needs_input_grad[0]:
+            dmp = dS32 @ Wsp
+            dmc = (dV32 @ Wv).double() + dg.wc[:, None] * dMG[dg.soc]          # mg_s = sum_{c in s} deg_c mc[c] / E_s
+            Bp = (dmp.double() * dg.invp[:, None]).float()
+            Ac = (dmc * dg.invc[:, None]).float()
+            dX = _native.sos_edge_dx(dY, Ym, Wp.contiguous(), edges.cam, edges.pt, Ac, Bp, X.shape[0], X.shape[1])
+        dWp = _native.sos_edge_dw(dY, Ym, X)
+        if U is not None:
+            dWp = (dWp.double() + U.t() @ MG).float()
+        dR = None
+        if ctx.has_R and ctx.needs_input_grad[9]:
+            dR = dY if Ym is None else dY * (Ym > 0)
+        return dX, dWp, dgrow32, dWsp, dbsp, dWv, dbv, dWg, dbg, dR, None, None, None
+
+    @staticmethod
     def backward(ctx, dY):
+        if ctx.union:
+            return SetOfSetLayerFn._backward_union(ctx, dY)
         X, Ym, Wp, Wsp, Wv, Wg, mp, mc, mg = ctx.saved_tensors
         edges, dg = ctx.edges, _degrees(ctx.edges)
         E = max(dg.E, 1)
@@ -164,6 +287,26 @@ class SetOfSetLayerFn(torch.autograd.Function):
         if ctx.has_R and ctx.needs_input_grad[9]:
             dR = dY if Ym is None else dY * (Ym > 0)
         return dX, dWp, dgrow32, dWsp, dbsp, dWv, dbv, dWg, dbg, dR, None, None, None
+
+
+class SceneCenterFn(torch.autograd.Function):
+    """X minus each scene's mean over its (contiguous) edge rows, for a union on the fused path: the
+    skip ProjLayer's centring.  The means are the ordered per-range column sums; centring is its own
+    adjoint, so the backward is the same operation on dY."""
+
+    @staticmethod
+    def _center(X, dg):
+        mean = _native.colsum_ranges(X, dg.ptre) / dg.Es[:, None]
+        return X - mean.float()[dg.soe]
+
+    @staticmethod
+    def forward(ctx, X, edges):
+        ctx.edges = edges
+        return SceneCenterFn._center(X.contiguous(), _degrees(edges))
+
+    @staticmethod
+    def backward(ctx, dY):
+        return SceneCenterFn._center(dY.contiguous(), _degrees(ctx.edges)), None
 
 
 # ------------------------------------------------------------------ modules (reference key names)
@@ -212,9 +355,12 @@ class SetOfSetLayer(Module):
                                          gfu.lin_global.bias, residual, edges, center, relu)
         mp, mc, mg = _composite_means(X, edges)
         S, V, g = gfu.lin_scenepoint(mp), gfu.lin_view(mc), gfu.lin_global(mg)
+        u = _union(edges)
+        if u is not None:  # one global row per scene
+            g = g[u.soe]
         Y = (lp(X) + S[edges.pt.long()] + V[edges.cam.long()] + g) / 4
         if center:
-            Y = Y - Y.mean(dim=0, keepdim=True) if Y.shape[0] else Y
+            Y = _center_rows(Y, edges)
         if residual is not None:
             Y = residual + Y
         return F.relu(Y) if relu else Y
@@ -240,7 +386,10 @@ class SetOfSetBlock(Module):
             if self.skip_projection is not None:
                 skip = dense.linear(X, self.skip_projection.lin_proj)
                 if self.proj_feat_normalization and skip.shape[0]:
-                    skip = skip - skip.mean(dim=0, keepdim=True)
+                    if not composite and skip.is_cuda and skip.dtype == torch.float32 and _union(edges) is not None:
+                        skip = SceneCenterFn.apply(skip, edges)
+                    else:
+                        skip = _center_rows(skip, edges)
         xl = X
         last = len(self.layers) - 1
         for i, layer in enumerate(self.layers):

@@ -330,6 +330,16 @@ int64_t gasfm_colsum_tall_ws_floats(int64_t rows, int32_t cols);
 int gasfm_colsum_tall(const float* A, int64_t rows, int32_t cols, float* ws, float* out,
                       uint32_t* counter, void* stream);
 
+/* out[s, j] = sum_{r = row_ptr[s]}^{row_ptr[s+1]-1} w[r] * A[r*ld + j] for s < n_ranges, j < cols
+ * (w null: plain sums): weighted column sums over contiguous row ranges, accumulated in fp64, ONE
+ * launch, no workspace, no atomics.  row_ptr: n_ranges + 1 non-decreasing device int32 row
+ * indices; w: one double per row of A, or null; out: [n_ranges, cols] doubles, every entry
+ * written (an empty range gives zeros).  Any cols >= 1 and ld >= cols; rows are read as float4
+ * when cols % 4 == 0, ld % 4 == 0 and A is 16-byte aligned.  The order of the additions depends
+ * on (row_ptr, cols) alone, so equal inputs give bitwise-equal sums, in a captured graph too. */
+int gasfm_colsum_ranges(const float* A, int64_t ld, int32_t cols, const int32_t* row_ptr,
+                        int32_t n_ranges, const double* w, double* out, void* stream);
+
 /* ---- fused per-edge block body (F = n_feat_proj = 32; XL width 64 = point|camera) ---- */
 
 /* Floats of the per-workgroup partial buffer: which = 0 -> edge_prologue_bwd
