@@ -177,6 +177,7 @@ _SIGS = {
     "gasfm_adam_step": (_i32, [_vp, _vp, _i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                ctypes.c_double, _i64, _vp]),
     "gasfm_union_fill_pad": (_i32, [_vp, _vp, _vp]),
+    "gasfm_sos_union_tables": (_i32, [_vp, _vp]),
     "gasfm_point_tail_part_shape": (_i32, [_i64, _i32, _vp]),
     "gasfm_point_hub_part_shape": (_i32, [_i64, _i32, _i32, _vp]),
     "gasfm_point_tail_fwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp]),
@@ -1369,6 +1370,47 @@ def adam_step(tensors, chunks, n_chunks, lr, beta1, beta2, eps, weight_decay, st
 
 def union_fill_pad(pd, out, stream_of):
     check(lib().gasfm_union_fill_pad(ctypes.byref(pd), ctypes.byref(out), _stream(stream_of)), "gasfm_union_fill_pad")
+
+
+_SOS_TABLES_IN = ("cam_ptr", "pt_ptr", "soc32", "sop32", "cam32", "eoff")
+_SOS_TABLES_I32 = ("ptrc", "ptrp", "ptre")
+_SOS_TABLES_F64 = ("Es", "degc", "invc", "wc", "degp", "invp", "wp")
+_SOS_TABLES_I64 = ("sop", "soe")
+
+
+class SosTables(ctypes.Structure):
+    _fields_ = ([(k, _vp) for k in _SOS_TABLES_IN] + [(k, _i64) for k in ("M", "N", "E")] + [("S", _i32)]
+                + [(k, _vp) for k in _SOS_TABLES_I32 + _SOS_TABLES_F64 + _SOS_TABLES_I64])
+
+
+def sos_tables_args(cam_ptr, pt_ptr, soc32, sop32, cam32, eoff, out):
+    """The gasfm_sos_tables of a union's static buffers (int32: cam_ptr [M + 1], pt_ptr [N + 1],
+    soc32 [M], sop32 [N], cam32 [E], eoff [S + 1]) and its table buffers ``out`` (attributes ptrc /
+    ptrp / ptre int32 [S + 1]; Es [S], degc / invc / wc [M], degp / invp / wp [N] fp64; sop [N],
+    soe [E] int64), every shape and type checked: built once per bucket, launched every step."""
+    M, N, E, S = soc32.numel(), sop32.numel(), cam32.numel(), eoff.numel() - 1
+    dev = soc32.device
+    want = dict(cam_ptr=M + 1, pt_ptr=N + 1, soc32=M, sop32=N, cam32=E, eoff=S + 1, ptrc=S + 1, ptrp=S + 1,
+                ptre=S + 1, Es=S, degc=M, invc=M, wc=M, degp=N, invp=N, wp=N, sop=N, soe=E)
+    given = dict(cam_ptr=cam_ptr, pt_ptr=pt_ptr, soc32=soc32, sop32=sop32, cam32=cam32, eoff=eoff)
+    if S < 1 or M < 1 or N < 1:
+        raise ValueError(f"sos_union_tables: S={S} M={M} N={N}")
+    t = SosTables()
+    for group, dtype in ((_SOS_TABLES_IN, torch.int32), (_SOS_TABLES_I32, torch.int32),
+                         (_SOS_TABLES_F64, torch.float64), (_SOS_TABLES_I64, torch.int64)):
+        for k in group:
+            v = given[k] if k in given else getattr(out, k)
+            if not (v.is_cuda and v.device == dev and v.dtype == dtype and v.dim() == 1 and v.is_contiguous()
+                    and v.numel() == want[k]):
+                raise ValueError(f"sos_union_tables: {k} must be a contiguous {dtype} CUDA vector of {want[k]} entries")
+            setattr(t, k, v.data_ptr())
+    t.M, t.N, t.E, t.S = M, N, E, S
+    return t
+
+
+def sos_union_tables(t, stream_of):
+    """One launch of gasfm_sos_union_tables on ``stream_of``'s current stream (t: sos_tables_args)."""
+    check(lib().gasfm_sos_union_tables(ctypes.byref(t), _stream(stream_of)), "gasfm_sos_union_tables")
 
 
 # ---------------------------------------------------------------- batched single-row problems (global hub)

@@ -41,11 +41,24 @@ class _Degrees:
     """Per-point / per-camera edge counts of a scene (float32 and float64), cached on its EdgeIndex.
     For a union of B scenes (B is not None) also the scenes' row ranges: int32 row pointers ptrc /
     ptrp / ptre, the scene of every camera / point / edge row soc / sop / soe, Es = max(E_s, 1) and
-    deg / E_s per camera and point (wc, wp)."""
+    deg / E_s per camera and point (wc, wp).  A batch.SceneBatch union builds them once from its host
+    offset lists; a static_batch.StaticBatch bucket supplies them as per-step device tables."""
+
+    # what a shape-stable union (static_batch.StaticBatch) hands over under plans["_scene_tables"]
+    TABLES = ("ptrc", "ptrp", "ptre", "ptr_all_c", "Es", "degc", "invc", "wc", "degp", "invp", "wp", "soc", "sop", "soe")
 
     def __init__(self, edges):
         pp, pc = edges.plans["proj2scenepoint"], edges.plans["proj2view"]
         self.E = int(edges.cam.shape[0])
+        tables = edges.plans.get("_scene_tables")
+        if tables is not None:
+            # a padded bucket: its contents change with every fill and a replayed graph reads nothing
+            # from the host, so the bucket owns these as static device buffers that every fill
+            # rewrites (gasfm_sos_union_tables); they are adopted, not rebuilt -- degrees included
+            self.B = int(tables.B)
+            for name in self.TABLES:
+                setattr(self, name, getattr(tables, name))
+            return
         for name, plan in (("p", pp), ("c", pc)):
             deg = (plan.seg_ptr[1:] - plan.seg_ptr[:-1]).to(torch.float64)
             setattr(self, "deg" + name, deg)
@@ -122,13 +135,14 @@ def _center_rows(Y, edges):
 
 def fusable(X, d_in, d_out, edges):
     """The fused kernels take this layer: fp32 CUDA rows of a covered width over plain plans (one
-    scene, or a batch.SceneBatch union with its per-scene row ranges)."""
+    scene, or a union with its per-scene row ranges: a batch.SceneBatch's host offsets or a
+    static_batch.StaticBatch's device tables)."""
     if not (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.shape[1] == d_in):
         return False
     pp, pc = edges.plans["proj2scenepoint"], edges.plans["proj2view"]
     if pp.all_partial or pc.all_partial or "_shard" in edges.plans:
         return False
-    if "_scene_of_cam" in edges.plans and "_scene_off" not in edges.plans:
+    if "_scene_of_cam" in edges.plans and "_scene_off" not in edges.plans and "_scene_tables" not in edges.plans:
         return False
     if pc.perm is not None or (pp.perm is not None and pp.perm.dtype != torch.int32):
         return False
@@ -440,6 +454,9 @@ class SetOfSetNet(BaseNet):
     composite = False
 
     def edge_index_for(self, data, device):
+        tables = getattr(data, "sos_tables", None)
+        if tables is not None:  # a static_batch.StaticBatch: its per-scene tables, made on first use
+            tables()
         return scene_edge_index(data, device)
 
     def forward(self, data):

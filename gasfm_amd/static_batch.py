@@ -163,6 +163,28 @@ def _inv3(Ns):
     return adj / det.view(-1, 1, 1)
 
 
+class SceneTables:
+    """What setofset's layers read of a union's scenes (setofset._Degrees, same names), as static
+    buffers of a bucket that every fill rewrites: row pointers ptrc / ptrp / ptre int32 [S + 1],
+    Es = max(E_s, 1) [S], deg / 1 / deg / deg / E_s per camera and point (fp64), the scene of every
+    camera / point / edge row (int64).  B counts the pad scene: it is a scene like the others."""
+
+    def __init__(self, sb):
+        c, dev = sb.caps, sb.device
+        z = lambda n, dtype: torch.zeros(n, dtype=dtype, device=dev)
+        self.B, self.E = c.S, c.E
+        self.ptrc, self.ptrp, self.ptre = (z(c.S + 1, torch.int32) for _ in range(3))
+        self.Es = torch.ones(c.S, dtype=torch.float64, device=dev)
+        self.degc, self.invc, self.wc = (z(c.M, torch.float64) for _ in range(3))
+        self.degp, self.invp, self.wp = (z(c.N, torch.float64) for _ in range(3))
+        self.soc = sb.scene_of_cam
+        self.sop, self.soe = z(c.N, torch.int64), z(c.E, torch.int64)
+        self.ptr_all_c = torch.tensor([0, c.M], dtype=torch.int32, device=dev)  # all cameras: one range
+        self.args = None
+        if dev.type == "cuda":
+            self.args = _native.sos_tables_args(sb.cam_ptr, sb.pt_ptr, sb.soc32, sb.sop32, sb.cam32, sb.eoff, self)
+
+
 class StaticBatch:
     """The static input buffers of one bucket, in the shape the model reads (``.x``, ``.graph_wrappers``,
     ``.scene_of_cam``), with the plans built over them once; ``fill`` writes a batch into them."""
@@ -250,6 +272,8 @@ class StaticBatch:
         # they ARE the static buffers, so a replay reads what fill() wrote
         plans = {n: w.plan for n, w in gw.items()}
         plans["_scene_of_cam"] = self.scene_of_cam
+        self._plans = plans
+        self._tables = None  # SceneTables, made by sos_tables() (SetOfSetNet only)
         self.x.__dict__["_gasfm_edges"] = {
             (str(dev), self.indices.data_ptr()): EdgeIndex(self.cam32, self.pt32, M, N, plans)}
         self.offsets = None
@@ -288,13 +312,50 @@ class StaticBatch:
         eo = np.concatenate([[0], np.cumsum(st.Es), [c.E]])
         return np.concatenate([items_s.ravel(), items_v.ravel(), seg_v, seg_p, eo]).astype(np.int32)
 
+    # ------------------------------------------------------------------ SetOfSetNet's per-scene tables
+    def sos_tables(self):
+        """The bucket's SceneTables, allocated on first use (GraphAttnSfMNet buckets never pay for
+        them) and handed to the set-of-set layers under plans["_scene_tables"].  From then on every
+        fill rewrites them; made after a fill, they are written for that fill's contents here."""
+        if self._tables is None:
+            self._tables = self._plans["_scene_tables"] = SceneTables(self)
+            if self.offsets is not None:
+                self._fill_tables()
+        return self._tables
+
+    def _fill_tables(self):
+        t = self._tables
+        if t.args is not None:
+            _native.sos_union_tables(t.args, self.values)
+        else:
+            self._tables_torch()
+
+    def _tables_torch(self):
+        """gasfm_sos_union_tables in torch ops, from the same static buffers."""
+        t, S = self._tables, self.caps.S
+        s = torch.arange(S + 1, dtype=torch.int32, device=self.device)
+        t.ptrc.copy_(torch.searchsorted(self.soc32, s))
+        t.ptrp.copy_(torch.searchsorted(self.sop32, s))
+        t.ptre.copy_(self.eoff)
+        eo = self.eoff.to(torch.int64)
+        t.Es.copy_((eo[1:] - eo[:-1]).clamp(min=1))
+        t.sop.copy_(self.sop32)
+        t.soe.copy_(self.scene_of_cam[self.cam32.long()])
+        for ptr, scene, deg, inv, w in ((self.cam_ptr, t.soc, t.degc, t.invc, t.wc),
+                                        (self.pt_ptr, t.sop, t.degp, t.invp, t.wp)):
+            d = (ptr[1:] - ptr[:-1]).to(torch.float64)
+            deg.copy_(d)
+            inv.copy_(torch.where(d > 0, 1.0 / d.clamp(min=1.0), torch.zeros_like(d)))
+            w.copy_(d / t.Es[scene])
+
     # ------------------------------------------------------------------ per-step fill
     def fill(self, datas, st, inputs=None):
         """Write the batch (device-built scenes; ``inputs``: the network's inputs when they differ from
         the loss's scenes, e.g. outlier-injected copies with the same edges) and this bucket's pad scene
         into the static buffers: one gasfm_union_fill_scene launch per scene, one gasfm_union_fill_pad,
-        one host-to-device copy of the global graphs' items.  fill_torch is the same in torch ops (the
-        CPU path, and the GPU test's check of this one)."""
+        one host-to-device copy of the global graphs' items, and one gasfm_sos_union_tables when the
+        bucket has SetOfSetNet's tables.  fill_torch is the same in torch ops (the CPU path, and the
+        GPU test's check of this one)."""
         c = self.caps
         if self._out is None:
             return self.fill_torch(datas, st, inputs)
@@ -352,6 +413,8 @@ class StaticBatch:
         else:
             self.eoff.copy_(torch.tensor(eo + [c.E], dtype=torch.int32).to(dev))
             self._global_plans_torch()
+        if self._tables is not None:  # reads eoff: after the copy above, on the same stream
+            _native.sos_union_tables(self._tables.args, self.values)
 
     def fill_torch(self, datas, st, inputs=None):
         """``fill`` in torch ops."""
@@ -452,6 +515,8 @@ class StaticBatch:
         pptr = self.pt_ptr.to(torch.int64)
         self.items_p.copy_(torch.stack([ar(c.N), pptr[:-1], pptr[1:], torch.full((c.N,), -1, **i64)], 1))
         self._global_plans_torch()
+        if self._tables is not None:
+            self._tables_torch()
 
     def _global_plans_torch(self):
         """view2global / scenepoint2global segments and items from the filled counts (torch ops)."""
@@ -676,3 +741,4 @@ class StaticTrainer:
         if not read_errors:
             return loss, err.clone()  # the static buffer is overwritten by the next replay
         return loss, self.errors(err)
+

@@ -944,6 +944,24 @@ typedef struct gasfm_union_pad {
 int gasfm_union_fill_scene(const gasfm_union_scene* scene, const gasfm_union_out* out, void* stream);
 int gasfm_union_fill_pad(const gasfm_union_pad* pad, const gasfm_union_out* out, void* stream);
 
+/* ---- per-step scene tables of a shape-stable union batch for SetOfSetNet (sos_tables.hip) ----
+ * One launch after the fill, from the static buffers it wrote (cam_ptr [M + 1], pt_ptr [N + 1], the
+ * sorted scene maps soc32 [M] / sop32 [N], cam32 [E], eoff [S + 1]) into buffers the bucket owns:
+ * ptrc / ptrp [S + 1] = the first camera / point row of each scene (lower bound of s in soc32 /
+ * sop32: an empty scene repeats the pointer, the last entry is M / N), ptre = eoff,
+ * Es [S] = max(eoff[s + 1] - eoff[s], 1), per camera and per point deg, inv = 1 / deg (0 where
+ * deg == 0) and w = deg / Es[scene], sop = sop32 widened and soe[e] = soc32[cam32[e]].  Every element
+ * is written by one thread from the inputs alone; each fp64 value is one division of integers. */
+typedef struct gasfm_sos_tables {
+  const int32_t *cam_ptr, *pt_ptr, *soc32, *sop32, *cam32, *eoff;
+  int64_t M, N, E;
+  int32_t S;
+  int32_t *ptrc, *ptrp, *ptre;
+  double *Es, *degc, *invc, *wc, *degp, *invp, *wp;
+  int64_t *sop, *soe;
+} gasfm_sos_tables;
+int gasfm_sos_union_tables(const gasfm_sos_tables* tables, void* stream);
+
 /* The same per scene of a union batch (eoff, S as gasfm_esfm_seg_fwd): tot[s] = (sum of the
  * non-NaN errors of scene s, their count); part: gasfm_esfm_seg_part_rows(S) x 2 floats. */
 int gasfm_reproj_error_seg(const int32_t* cam, const int32_t* pt, const float* xy, const int32_t* eoff, int32_t S,

@@ -1,6 +1,6 @@
 """Multi-scene learning step (BASELINE config 3 shape) with the whole per-sample data path on the device.
 
-usage: python tools/train_step_bench.py [--scenes 12] [--batch 4] [--steps 10] [--host]
+usage: python tools/train_step_bench.py [--scenes 12] [--batch 4] [--steps 10] [--host] [--model gasfm|setofset]
 
 Synthetic stand-ins for the 12 Euclidean training scenes (windowed visibility, m = 100 views,
 n = 20k points, dense M resident in HBM).  One step follows train.py:60-140 for a batch of
@@ -13,6 +13,8 @@ union of the scene graphs (gasfm_amd/batch.py); --per-scene also times train.py'
 scene.  Every per-sample stage runs on the device
 (scene_device.py, loss.py, evaluation.py); --host instead samples on the CPU and builds the graph
 with the host builder (no augmentation), the way the reference's DataLoader workers feed the GPU.
+--model setofset runs the DPESFM baseline (setofset.SetOfSetNet, the shipped dpesfm conf) through the eager
+modes (StaticTrainer, i.e. --captured / --pipeline, takes GraphAttnSfMNet only).
 Prints one JSON line per mode: scenes/s and the mean ms per stage.
 """
 import argparse
@@ -54,6 +56,8 @@ def main():
     ap.add_argument("--views", type=int, default=100)
     ap.add_argument("--points", type=int, default=20_000)
     ap.add_argument("--host", action="store_true", help="also time the host-side data path")
+    ap.add_argument("--model", choices=("gasfm", "setofset"), default="gasfm",
+                    help="the net: GraphAttnSfMNet (learning conf) or the DPESFM baseline SetOfSetNet (dpesfm conf)")
     ap.add_argument("--outliers", type=float, default=0.0,
                     help="outlier injection rate (config 5: rhaug-15-20 + 0.1 outliers), 0 = off")
     ap.add_argument("--per-scene", action="store_true",
@@ -75,17 +79,19 @@ def main():
                     help="also time one FIXED batch's forward + loss + backward captured as a hipGraph and "
                          "replayed (the GPU-side floor of the union step, without the host's launch cost)")
     args = ap.parse_args()
+    if args.model != "gasfm" and (args.captured or args.pipeline):
+        ap.error("--captured / --pipeline: StaticTrainer takes GraphAttnSfMNet only")
     dev = torch.device("cuda", 0)
     np.random.seed(0)
     torch.manual_seed(0)
     scenes = make_scenes(args.scenes, args.views, args.points, dev)
-    base = gasfm_amd.learning_conf()
+    base = gasfm_amd.learning_conf() if args.model == "gasfm" else gasfm_amd.dpesfm_conf()
     conf = Conf({"dataset": {"calibrated": True}, "model": base.d["model"],
                  "loss": {"infinity_pts_margin": 1e-4, "pts_grad_equalization_pre_perspective_divide": True,
                           "normalize_grad_wrt_valid_projections_only": True, "hinge_loss": True,
                           "hinge_loss_weight": 1.0},
                  "eval": {"calc_reprojerr_with_gtposes_for_depth_pred": False}})
-    net = gasfm_amd.GraphAttnSfMNet(conf).to(dev)
+    net = (gasfm_amd.GraphAttnSfMNet if args.model == "gasfm" else gasfm_amd.SetOfSetNet)(conf).to(dev)
     lossf = ESFMLoss(conf)
     # torch's fused Adam (one kernel chain over all 145M parameters; train.py uses Adam's default foreach)
     opt = torch.optim.Adam(net.parameters(), lr=1e-4, fused=True)
@@ -258,6 +264,8 @@ def main():
                 "last_repro_px": float(repro[-1])}
 
     tag = f" + {args.outliers:g} outlier injection" if args.outliers else ""
+    if args.model != "gasfm":
+        tag += f", model {args.model}"
     if not args.no_eager:
         res = run(prep_device, args.steps, args.warmup)
         print(json.dumps({"mode": "device data path (sample + rhaug" + tag + " + graph build on GPU), batch as one union forward",
