@@ -667,7 +667,7 @@ def _ld_stat(seg_max):
 def edge_seam_fwd(Pb, P0, pt, lnw_b, lnb_b, eps_b, Wp, bp, Sp, Sv, Sg, scale, Pout, ln_w, ln_b, eps, Wpt, bpt, Wc, bc,
                   XLp, pos, XR, att, bias, slope, plan_items, n_items, finalize, out, seg_max, seg_sum, part):
     """Block b's edge epilogue (P' = Pout) + block b+1's prologue and camera attention forward in one
-    pass (csrc/edge_cam.hip edge_seam_fwd); outputs as edge_cam_fwd's plus Pout."""
+    pass (csrc/edge_seam.hip edge_seam_fwd_kernel); outputs as edge_cam_fwd's plus Pout."""
     _req(Pb, "Pb", 32)
     ldXR = _rows32(XR, "XR")
     ldSv = _rows32(Sv, "Sv")
@@ -684,7 +684,7 @@ def edge0_seam_fwd(P, pt, lna_w, lna_b, lnb_w, lnb_b, eps0, Wp, bp, Wsk, bsk, Sp
                    Wpt, bpt, Wc, bc, XLp, pos, XR, att, bias, slope, plan_items, n_items, finalize, out, seg_max,
                    seg_sum, part):
     """Block 0's edge epilogue (2-wide P, edge0_epilogue_fwd) + block 1's prologue and camera
-    attention forward in one pass (csrc/edge_cam.hip edge_seam_fwd, EP0); outputs as
+    attention forward in one pass (csrc/edge_seam.hip edge_seam_fwd_kernel, EP0); outputs as
     edge_seam_fwd's."""
     _req(P, "P", 2)
     ldXR = _rows32(XR, "XR")
