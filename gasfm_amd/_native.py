@@ -167,6 +167,17 @@ _SIGS = {
                                   _vp]),
     "gasfm_esfm_seg_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _f32,
                                   _f32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "gasfm_ose_part_rows": (_i32, [_i64]),
+    "gasfm_ose_fwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _f32, _vp, _vp]),
+    "gasfm_ose_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "gasfm_ose_seg_part_rows": (_i32, [_i32]),
+    "gasfm_ose_seg_fwd": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "gasfm_ose_seg_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _f32,
+                                 _vp, _vp, _vp, _vp]),
+    "gasfm_depth_loss_part_rows": (_i32, [_i64]),
+    "gasfm_depth_loss_sums": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    "gasfm_depth_loss_fwd": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp]),
+    "gasfm_depth_loss_bwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
     "gasfm_reproj_error_seg": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "gasfm_depth_stats_ws_doubles": (_i64, [_i64]),
     "gasfm_depth_stats": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
@@ -1308,6 +1319,93 @@ def esfm_seg_bwd(cptr, pptr, perm, cam, pt, vals, eoff, scene_of_cam, scene_of_p
                                   int(hinge), int(equalize), int(valid_only), _p(dloss), _p(tot), _p(dP), _p(dX),
                                   _stream(X))
     check(st, "gasfm_esfm_seg_bwd")
+
+
+# ------------------------------------------- ExpDepthRegularizedOSELoss (ose_loss.hip)
+def ose_fwd(cam, pt, vals, P, X, w_reg):
+    """Per-workgroup sums [rows, 1] of the OSE + exp-depth terms (finish with colsum)."""
+    E, n = cam.shape[0], X.shape[1]
+    _i32vec(cam, "cam"), _i32vec(pt, "pt")
+    _req(vals, "vals", 2), _req(P, "P", 12), _req(X, "pts3D", n)
+    if X.shape[0] != 4 or pt.shape[0] != E or vals.shape[0] != E:
+        raise ValueError("ose_fwd: expected pts3D [4, n] and E-long cam / pt / values")
+    part = torch.empty((lib().gasfm_ose_part_rows(E), 1), dtype=torch.float32, device=X.device)
+    st = lib().gasfm_ose_fwd(_p(cam), _p(pt), _p(vals), E, _p(P), _p(X), n, w_reg, _p(part), _stream(X))
+    check(st, "gasfm_ose_fwd")
+    return part
+
+
+def ose_bwd(cptr, pptr, perm, cam, pt, vals, P, X, w_reg, dloss, dP, dX):
+    E, n, m = cam.shape[0], X.shape[1], P.shape[0]
+    for t, name in ((cptr, "cam_ptr"), (pptr, "pt_ptr"), (cam, "cam"), (pt, "pt")):
+        _i32vec(t, name)
+    if perm is not None:
+        _i32vec(perm, "perm")
+    if cptr.shape[0] != m + 1 or pptr.shape[0] != n + 1 or (perm is not None and perm.shape[0] != E):
+        raise ValueError("ose_bwd: CSR shapes do not match m / n / E")
+    _req(vals, "vals", 2), _req(dloss, "dloss"), _req(dP, "dP", 12), _req(dX, "dX", n)
+    st = lib().gasfm_ose_bwd(_p(cptr), m, _p(pptr), _p(perm), _p(cam), _p(pt), _p(vals), E, _p(P), _p(X), n, w_reg,
+                             _p(dloss), _p(dP), _p(dX), _stream(X))
+    check(st, "gasfm_ose_bwd")
+
+
+def ose_seg_fwd(cam, pt, vals, eoff, weight, P, X, w_reg):
+    """Union-batch OSE loss forward (gasfm_ose_seg_fwd): (loss [1], tot [S])."""
+    S = int(weight.numel())
+    _seg_args(eoff, S, "ose_seg_fwd")
+    n = X.shape[1]
+    if X.shape[0] != 4 or cam.shape != pt.shape or vals.shape != (cam.shape[0], 2):
+        raise ValueError("ose_seg_fwd: expected pts3D [4, n] and E-long cam / pt / values")
+    dev = X.device
+    part = torch.empty(lib().gasfm_ose_seg_part_rows(S), dtype=torch.float32, device=dev)
+    tot = torch.empty(S, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    st = lib().gasfm_ose_seg_fwd(_p(cam), _p(pt), _p(vals), _p(eoff), S, _p(weight), _p(P), _p(X), n, w_reg, _p(part),
+                                 _p(tot), _p(loss), _stream(X))
+    check(st, "gasfm_ose_seg_fwd")
+    return loss, tot
+
+
+def ose_seg_bwd(cptr, pptr, perm, cam, pt, vals, eoff, scene_of_cam, scene_of_pt, weight, P, X, w_reg, dloss, dP, dX):
+    """Union-batch OSE loss backward (gasfm_ose_seg_bwd) into dP [m, 12] and dX [4, n]."""
+    S = int(weight.numel())
+    _seg_args(eoff, S, "ose_seg_bwd")
+    m, n = P.shape[0], X.shape[1]
+    if cptr.numel() != m + 1 or pptr.numel() != n + 1 or scene_of_cam.numel() != m or scene_of_pt.numel() != n:
+        raise ValueError("ose_seg_bwd: CSR / scene map shapes do not match m / n")
+    st = lib().gasfm_ose_seg_bwd(_p(cptr), m, _p(pptr), _p(perm), _p(cam), _p(pt), _p(vals), _p(eoff), S,
+                                 _p(scene_of_cam), _p(scene_of_pt), _p(weight), _p(P), _p(X), n, w_reg, _p(dloss),
+                                 _p(dP), _p(dX), _stream(X))
+    check(st, "gasfm_ose_seg_bwd")
+
+
+# ------------------------------------------- DirectDepthLoss (depth_loss.hip)
+def _depth_args(a, b, name):
+    _req(a, "depths"), _req(b, "depth targets")
+    if a.dim() != 1 or a.shape != b.shape or a.shape[0] == 0:
+        raise ValueError(f"{name}: expected two non-empty [E] vectors, got {tuple(a.shape)}, {tuple(b.shape)}")
+
+
+def depth_loss_fwd(a, b, l2):
+    """(sums [2] = (sum a, sum b), tot [2] = (sum of terms, sum of g_e a_e)) of DirectDepthLoss."""
+    _depth_args(a, b, "depth_loss_fwd")
+    E, L = a.shape[0], lib()
+    part = torch.empty((L.gasfm_depth_loss_part_rows(E), 2), dtype=torch.float32, device=a.device)
+    check(L.gasfm_depth_loss_sums(_p(a), _p(b), E, _p(part), _stream(a)), "gasfm_depth_loss_sums")
+    sums = colsum(part)
+    part = torch.empty_like(part)
+    check(L.gasfm_depth_loss_fwd(_p(a), _p(b), E, _p(sums), int(l2), _p(part), _stream(a)), "gasfm_depth_loss_fwd")
+    return sums, colsum(part)
+
+
+def depth_loss_bwd(a, b, sums, tot, l2, dloss):
+    _depth_args(a, b, "depth_loss_bwd")
+    _req(dloss, "dloss")
+    da = torch.empty_like(a)
+    st = lib().gasfm_depth_loss_bwd(_p(a), _p(b), a.shape[0], _p(sums), _p(tot), int(l2), _p(dloss), _p(da),
+                                    _stream(a))
+    check(st, "gasfm_depth_loss_bwd")
+    return da
 
 
 def reproj_error_seg(cam, pt, xy, eoff, S, P, X):

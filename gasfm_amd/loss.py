@@ -18,6 +18,10 @@ is gone, so the loss can sit inside a captured step.
 The measurement of edge e is ``data.x.values[e]``: M2sparse(normalize=True) (dataset_utils.py:116)
 stores exactly the entries of ``data.norm_M`` (geo_utils.normalize_M, geo_utils.py:689) at the
 valid positions, in the same cam-major order as ``data.x.indices``.
+
+The reference's other training losses follow the same scheme: ``ExpDepthRegularizedOSELoss``
+(csrc/ose_loss.hip, also over a union batch: static_batch.batch_loss) and ``DirectDepthLoss``
+(csrc/depth_loss.hip); ``get_loss_func(conf)`` picks the loss ``loss.func`` names.
 """
 import torch
 
@@ -135,3 +139,157 @@ class ESFMLoss(torch.nn.Module):
             raise ValueError("ESFMLoss: a sharded scene must carry n_edges_global (distributed.shard_scene)")
         return ESFMLossFn.apply(Ps, pts3D, edges, vals, cam_ptr, pt_ptr, pt_perm, self.kernel_conf(), shard,
                                 E_global)
+
+
+def _check_projection_inputs(name, Ps, pts3D):
+    for t, tname in ((Ps, "Ps_norm"), (pts3D, "pts3D")):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise TypeError(f"{name}: {tname} must be a float32 CUDA tensor (no CPU fallback)")
+    if Ps.dim() != 3 or tuple(Ps.shape[1:]) != (3, 4) or pts3D.dim() != 2 or pts3D.shape[0] != 4:
+        raise ValueError(f"{name}: expected Ps_norm [m, 3, 4] and pts3D [4, n], got {tuple(Ps.shape)}, "
+                         f"{tuple(pts3D.shape)}")
+
+
+class OSELossFn(torch.autograd.Function):
+    """(Ps [m, 3, 4], pts3D [4, n]) -> mean over the edges of ||y_xy - y_z m_e|| + w_reg exp(-y_z)
+    (csrc/ose_loss.hip)."""
+
+    @staticmethod
+    def forward(ctx, Ps, pts3D, edges, vals, cam_ptr, pt_ptr, pt_perm, w_reg):
+        cam, pt = edges
+        P = Ps.reshape(Ps.shape[0], 12).contiguous()
+        X = pts3D.contiguous()
+        tot = _native.colsum(_native.ose_fwd(cam, pt, vals, P, X, w_reg))
+        ctx.save_for_backward(P, X, cam, pt, vals, cam_ptr, pt_ptr, pt_perm)
+        ctx.w_reg = w_reg
+        return tot[0] / cam.shape[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        P, X, cam, pt, vals, cam_ptr, pt_ptr, pt_perm = ctx.saved_tensors
+        dP, dX = torch.empty_like(P), torch.empty_like(X)
+        dloss = dloss.reshape(1).to(torch.float32).contiguous()
+        _native.ose_bwd(cam_ptr, pt_ptr, pt_perm, cam, pt, vals, P, X, ctx.w_reg, dloss, dP, dX)
+        return dP.view(-1, 3, 4), dX, None, None, None, None, None, None
+
+
+class ExpDepthRegularizedOSELoss(torch.nn.Module):
+    """The reference's ``loss_functions.ExpDepthRegularizedOSELoss`` (code/loss_functions.py:126-150):
+    object space error plus ``loss.depth_regul_weight * exp(-depth)``, a smooth loss with no barrier
+    at the principal plane, over the visibility edges instead of the dense [m, 3, n] projections."""
+
+    def __init__(self, conf):
+        super().__init__()
+        assert conf.get_bool("model.view_head.enabled", default=False)
+        assert conf.get_bool("model.scenepoint_head.enabled", default=False)
+        self.depth_regul_weight = conf.get_float("loss.depth_regul_weight")
+
+    def forward(self, pred_dict, data, epoch=None):
+        Ps, pts3D = pred_dict["Ps_norm"], pred_dict["pts3D"]
+        _check_projection_inputs("ExpDepthRegularizedOSELoss", Ps, pts3D)
+        if getattr(data, "shard", None) is not None:
+            raise ValueError("ExpDepthRegularizedOSELoss: point-sharded scenes are not supported")
+        edges, vals, cam_ptr, pt_ptr, pt_perm = _edge_tensors(data)
+        if edges[0].shape[0] == 0:
+            raise ValueError("ExpDepthRegularizedOSELoss: no valid observations (the reference's mean would be NaN)")
+        return OSELossFn.apply(Ps, pts3D, edges, vals, cam_ptr, pt_ptr, pt_perm, float(self.depth_regul_weight))
+
+
+class DepthLossFn(torch.autograd.Function):
+    """(a [E], b [E]) -> mean |a / mean a - b / mean b| or its square (csrc/depth_loss.hip)."""
+
+    @staticmethod
+    def forward(ctx, a, b, l2):
+        a = a.contiguous()
+        sums, tot = _native.depth_loss_fwd(a, b, l2)
+        ctx.save_for_backward(a, b, sums, tot)
+        ctx.l2 = l2
+        return tot[0] / a.shape[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        a, b, sums, tot = ctx.saved_tensors
+        dloss = dloss.reshape(1).to(torch.float32).contiguous()
+        return _native.depth_loss_bwd(a, b, sums, tot, ctx.l2, dloss), None, None
+
+
+def _edge_depth_targets(data, indices):
+    """float32 [E] target depths in edge order from ``data.depths``: a per-edge [E] tensor as it is,
+    or the reference's dense [m, n] tensor gathered at ``indices`` on the device, once (cached like
+    _edge_tensors' indices, keyed on both tensors' storage and version)."""
+    dep = getattr(data, "depths", None)
+    if dep is None:
+        raise ValueError("DirectDepthLoss: the scene carries no data.depths")
+    E = indices.shape[1]
+    if dep.dim() == 1:
+        if dep.shape[0] != E:
+            raise ValueError(f"DirectDepthLoss: per-edge data.depths has {dep.shape[0]} entries for {E} edges")
+        if not dep.is_cuda or dep.dtype != torch.float32:
+            raise TypeError("DirectDepthLoss: per-edge data.depths must be a float32 CUDA tensor")
+        return dep.contiguous()
+    if dep.dim() != 2:
+        raise ValueError(f"DirectDepthLoss: data.depths must be [m, n] or [E], got {tuple(dep.shape)}")
+    caches = scene_csr(data)[0]
+    key = (dep.data_ptr(), dep._version, tuple(dep.shape), indices.data_ptr(), indices._version, E)
+    cache = caches.get("depth_targets")
+    if cache is None or cache[0] != key:
+        cache = (key, dep.to(indices.device)[indices[0], indices[1]].float().contiguous())
+        caches["depth_targets"] = cache
+    return cache[1]
+
+
+class DirectDepthLoss(torch.nn.Module):
+    """The reference's ``loss_functions.DirectDepthLoss`` (code/loss_functions.py:24-66): L1 / L2
+    distance of the mean-normalised predicted and target depths of the observed projections."""
+
+    def __init__(self, conf):
+        super().__init__()
+        assert conf.get_bool("model.depth_head.enabled")
+        self.cost_fcn = conf.get_string("loss.cost_fcn")
+        assert self.cost_fcn in ["L1", "L2"]
+        if not conf.get_bool("dataset.calibrated"):
+            raise NotImplementedError("DirectDepthLoss: uncalibrated data (as the reference)")
+
+    def forward(self, pred_dict, data, epoch=None):
+        dep = pred_dict["depths"]
+        a = dep.values
+        if not a.is_cuda or a.dtype != torch.float32:
+            raise TypeError("DirectDepthLoss: depths must be a float32 CUDA tensor (no CPU fallback)")
+        if a.dim() != 2 or a.shape[1] != 1:
+            raise ValueError(f"DirectDepthLoss: expected depths values [E, 1], got {tuple(a.shape)}")
+        if a.shape[0] == 0:
+            raise ValueError("DirectDepthLoss: no valid observations (the reference's mean would be NaN)")
+        b = _edge_depth_targets(data, dep.indices)
+        return DepthLossFn.apply(a[:, 0], b, self.cost_fcn == "L2")
+
+
+class GTLoss(torch.nn.Module):
+    def __init__(self, conf):
+        raise NotImplementedError(
+            "GTLoss is not built: it is camera-sized with no hot path, and the reference's calibrated branch "
+            "calls geo_utils.rot_to_quat, which does not exist in the reference tree, so there is nothing to "
+            "check a port against")
+
+
+_LOSSES = {"ESFMLoss": ESFMLoss, "ExpDepthRegularizedOSELoss": ExpDepthRegularizedOSELoss, "GTLoss": GTLoss,
+           "DirectDepthLoss": DirectDepthLoss}
+
+
+def get_loss_func(conf):
+    """The reference's ``loss_functions.get_loss_func`` (code/loss_functions.py:8-21): the loss
+    ``loss.func`` names, after checking that the enabled heads are the ones it trains."""
+    spec = conf.get_string("loss.func")
+    if spec in ("ESFMLoss", "ExpDepthRegularizedOSELoss", "GTLoss"):
+        assert conf.get_bool("model.view_head.enabled")
+        assert conf.get_bool("model.scenepoint_head.enabled")
+        assert not conf.get_bool("model.depth_head.enabled"), \
+            "Make sure that model.depth_head.enabled=False, if there is no loss applied on such output."
+    elif spec == "DirectDepthLoss":
+        assert conf.get_bool("model.depth_head.enabled")
+        assert not conf.get_bool("model.view_head.enabled"), \
+            "Make sure that model.view_head.enabled=False, if there is no loss applied on such output."
+        assert not conf.get_bool("model.scenepoint_head.enabled"), \
+            "Make sure that model.scenepoint_head.enabled=False, if there is no loss applied on such output."
+    else:
+        assert False, "Unknown loss function: {}.".format(spec)
+    return _LOSSES[spec](conf)

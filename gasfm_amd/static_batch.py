@@ -582,8 +582,38 @@ class BatchLossFn(torch.autograd.Function):
         return dP.view(-1, 3, 4), dX, None, None
 
 
+class BatchOSELossFn(torch.autograd.Function):
+    """sum over the real scenes of ExpDepthRegularizedOSELoss(pred, scene) on a StaticBatch
+    (gasfm_ose_seg_fwd / _bwd), as BatchLossFn."""
+
+    @staticmethod
+    def forward(ctx, Ps, pts3D, sb, w_reg):
+        P = Ps.reshape(Ps.shape[0], 12).contiguous()
+        X = pts3D.contiguous()
+        loss, _ = _native.ose_seg_fwd(sb.cam32, sb.pt32, sb.values_loss, sb.eoff, sb.weight, P, X, w_reg)
+        ctx.save_for_backward(P, X)
+        ctx.sb, ctx.w_reg = sb, w_reg
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        P, X = ctx.saved_tensors
+        sb = ctx.sb
+        dP, dX = torch.empty_like(P), torch.empty_like(X)
+        dloss = dloss.reshape(1).to(torch.float32).contiguous()
+        _native.ose_seg_bwd(sb.cam_ptr, sb.pt_ptr, sb.perm, sb.cam32, sb.pt32, sb.values_loss, sb.eoff, sb.soc32,
+                            sb.sop32, sb.weight, P, X, ctx.w_reg, dloss, dP, dX)
+        return dP.view(-1, 3, 4), dX, None, None
+
+
 def batch_loss(pred, sb, lossf):
-    return BatchLossFn.apply(pred["Ps_norm"], pred["pts3D"], sb, lossf.kernel_conf())
+    from .loss import ESFMLoss, ExpDepthRegularizedOSELoss
+    if isinstance(lossf, ESFMLoss):
+        return BatchLossFn.apply(pred["Ps_norm"], pred["pts3D"], sb, lossf.kernel_conf())
+    if isinstance(lossf, ExpDepthRegularizedOSELoss):
+        return BatchOSELossFn.apply(pred["Ps_norm"], pred["pts3D"], sb, float(lossf.depth_regul_weight))
+    raise TypeError(f"batch_loss: no union-batch form of {type(lossf).__name__} (ESFMLoss and "
+                    "ExpDepthRegularizedOSELoss have one)")
 
 
 def batch_repro_errors(pred, sb):

@@ -710,6 +710,48 @@ int gasfm_esfm_seg_bwd(const int32_t* cam_ptr, int32_t m, const int32_t* pt_ptr,
                        int32_t valid_only, const float* dloss, const float* tot, float* dP, float* dpts3D,
                        void* stream);
 
+/* ---- ExpDepthRegularizedOSELoss over the visibility edges (ose_loss.hip) ----
+ * Replaces ExpDepthRegularizedOSELoss.forward (code/loss_functions.py:138-150) and its autograd
+ * backward through the dense [m, 3, n] projections.  Arguments as gasfm_esfm_fwd / _bwd; per edge
+ * y = P[cam] @ pts3D[:, pt], r = y_xy - y_z * vals[e], term = ||r|| + w_reg * exp(-y_z)
+ * (w_reg = loss.depth_regul_weight).  Forward writes gasfm_ose_part_rows(E) floats of
+ * per-workgroup sums; their sum is E * loss.  Backward reads dloss[0] from device memory and
+ * writes dP [m, 12] and dpts3D [4, n]; the norm's gradient is 0 where r = 0. */
+int32_t gasfm_ose_part_rows(int64_t E);
+int gasfm_ose_fwd(const int32_t* cam, const int32_t* pt, const float* vals, int64_t E, const float* P,
+                  const float* pts3D, int64_t n, float w_reg, float* part, void* stream);
+int gasfm_ose_bwd(const int32_t* cam_ptr, int32_t m, const int32_t* pt_ptr, const int32_t* perm, const int32_t* cam,
+                  const int32_t* pt, const float* vals, int64_t E, const float* P, const float* pts3D, int64_t n,
+                  float w_reg, const float* dloss, float* dP, float* dpts3D, void* stream);
+
+/* The same over a union batch of S scenes (layout, weights and the zero-weight pad scene as
+ * gasfm_esfm_seg_fwd / _bwd): tot[s] = sum of scene s's terms, loss[0] = sum over the scenes with
+ * weight[s] != 0 of weight[s] * tot[s] / E_s; part: gasfm_ose_seg_part_rows(S) floats of
+ * workspace.  S <= 256.  Fixed launch geometry for a given S. */
+int32_t gasfm_ose_seg_part_rows(int32_t S);
+int gasfm_ose_seg_fwd(const int32_t* cam, const int32_t* pt, const float* vals, const int32_t* eoff, int32_t S,
+                      const float* weight, const float* P, const float* pts3D, int64_t n, float w_reg, float* part,
+                      float* tot, float* loss, void* stream);
+int gasfm_ose_seg_bwd(const int32_t* cam_ptr, int32_t m, const int32_t* pt_ptr, const int32_t* perm,
+                      const int32_t* cam, const int32_t* pt, const float* vals, const int32_t* eoff, int32_t S,
+                      const int32_t* scene_of_cam, const int32_t* scene_of_pt, const float* weight, const float* P,
+                      const float* pts3D, int64_t n, float w_reg, const float* dloss, float* dP, float* dpts3D,
+                      void* stream);
+
+/* ---- DirectDepthLoss over the visibility edges (depth_loss.hip) ----
+ * Replaces DirectDepthLoss.forward (code/loss_functions.py:36-66): a = predicted, b = target depth
+ * per edge, u = a / mean(a) - b / mean(b), loss = mean |u| (l2 = 0) or mean u^2 (l2 != 0).
+ * gasfm_depth_loss_sums writes gasfm_depth_loss_part_rows(E) rows of (sum a, sum b); their column
+ * sums are `sums`.  gasfm_depth_loss_fwd reads `sums` from device memory and writes the same number
+ * of rows of (sum of terms, sum of g_e a_e), g = sign(u) or 2u; their column sums are `tot`
+ * (loss = tot[0] / E).  gasfm_depth_loss_bwd writes da [E] from dloss[0], sums and tot. */
+int32_t gasfm_depth_loss_part_rows(int64_t E);
+int gasfm_depth_loss_sums(const float* a, const float* b, int64_t E, float* part, void* stream);
+int gasfm_depth_loss_fwd(const float* a, const float* b, int64_t E, const float* sums, int32_t l2, float* part,
+                         void* stream);
+int gasfm_depth_loss_bwd(const float* a, const float* b, int64_t E, const float* sums, const float* tot, int32_t l2,
+                         const float* dloss, float* da, void* stream);
+
 /* ---- global node (ONE row): LayerNorm -> ReLU -> Linear (+ residual) ----
  * Replaces the M = 1 aten chains on the global feature vector: norm_and_proj_global2view /
  * _global2scenepoint (layers.py:497-520), both convs' lin_r on those rows (PyG),

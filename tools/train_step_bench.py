@@ -32,7 +32,6 @@ from gasfm_amd import evaluation, synthetic  # noqa: E402
 from gasfm_amd.batch import forward_batch  # noqa: E402
 from gasfm_amd.outliers import inject_outliers  # noqa: E402
 from gasfm_amd.conf import Conf  # noqa: E402
-from gasfm_amd.loss import ESFMLoss  # noqa: E402
 from gasfm_amd.scene_device import (apply_rotational_homography_aug_device, sample_data_device,  # noqa: E402
                                     sample_indices, scene_from_dense_device)
 
@@ -78,6 +77,8 @@ def main():
     ap.add_argument("--capture-floor", action="store_true",
                     help="also time one FIXED batch's forward + loss + backward captured as a hipGraph and "
                          "replayed (the GPU-side floor of the union step, without the host's launch cost)")
+    ap.add_argument("--loss", choices=("esfm", "ose"), default="esfm",
+                    help="loss.func: ESFMLoss (default) or ExpDepthRegularizedOSELoss (depth_regul_weight 0.1)")
     args = ap.parse_args()
     if args.model != "gasfm" and (args.captured or args.pipeline):
         ap.error("--captured / --pipeline: StaticTrainer takes GraphAttnSfMNet only")
@@ -89,10 +90,11 @@ def main():
     conf = Conf({"dataset": {"calibrated": True}, "model": base.d["model"],
                  "loss": {"infinity_pts_margin": 1e-4, "pts_grad_equalization_pre_perspective_divide": True,
                           "normalize_grad_wrt_valid_projections_only": True, "hinge_loss": True,
-                          "hinge_loss_weight": 1.0},
+                          "hinge_loss_weight": 1.0, "depth_regul_weight": 0.1,
+                          "func": {"esfm": "ESFMLoss", "ose": "ExpDepthRegularizedOSELoss"}[args.loss]},
                  "eval": {"calc_reprojerr_with_gtposes_for_depth_pred": False}})
     net = (gasfm_amd.GraphAttnSfMNet if args.model == "gasfm" else gasfm_amd.SetOfSetNet)(conf).to(dev)
-    lossf = ESFMLoss(conf)
+    lossf = gasfm_amd.get_loss_func(conf)
     # torch's fused Adam (one kernel chain over all 145M parameters; train.py uses Adam's default foreach)
     opt = torch.optim.Adam(net.parameters(), lr=1e-4, fused=True)
 
