@@ -1204,10 +1204,45 @@ def pose_bwd(x, dP, dx):
           "gasfm_pose_bwd")
 
 
-# ---------------------------------------------------------------- ESFMLoss (esfm_loss.hip)
+# ------------------- per-edge losses and metrics (edge_loss.hpp: esfm_loss.hip, ose_loss.hip)
 def _i32vec(t, name):
     if not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
         raise TypeError(f"{name}: expected a contiguous int32 CUDA vector")
+
+
+def _edge_args(name, cam, pt, vals, P, X, csr=None, seg=None, scene_of=None, f32=()):
+    """Validate the argument family of the per-edge kernels and return (E, m, n): int32 vectors cam /
+    pt [E], vals [E, 2], P [m, 12], X [4, n]; ``csr`` = (cam_ptr [m + 1], pt_ptr [n + 1], perm [E] or
+    None); ``seg`` = (eoff [S + 1], S); ``scene_of`` = the (camera [m], point [n]) scene maps; ``f32`` =
+    further (tensor, name, columns or None) float32 operands."""
+    vecs = [(cam, "cam"), (pt, "pt")]
+    if csr is not None:
+        vecs += [(csr[0], "cam_ptr"), (csr[1], "pt_ptr")] + ([] if csr[2] is None else [(csr[2], "perm")])
+    if scene_of is not None:
+        vecs += [(scene_of[0], "scene_of_cam"), (scene_of[1], "scene_of_pt")]
+    for t, tname in vecs:
+        _i32vec(t, f"{name}: {tname}")
+    for t, tname, cols in ((vals, "vals", 2), (P, "P", 12), (X, "pts3D", None)) + tuple(f32):
+        _req(t, f"{name}: {tname}", cols)
+    if X.dim() != 2 or X.shape[0] != 4 or P.dim() != 2 or vals.dim() != 2:
+        raise ValueError(f"{name}: expected P [m, 12], pts3D [4, n] and vals [E, 2]")
+    E, m, n = cam.shape[0], P.shape[0], X.shape[1]
+    if pt.shape[0] != E or vals.shape[0] != E:
+        raise ValueError(f"{name}: expected pts3D [4, n] and E-long cam / pt / values")
+    if csr is not None and (csr[0].shape[0] != m + 1 or csr[1].shape[0] != n + 1
+                            or (csr[2] is not None and csr[2].shape[0] != E)):
+        raise ValueError(f"{name}: CSR shapes do not match m / n / E")
+    if scene_of is not None and (scene_of[0].shape[0] != m or scene_of[1].shape[0] != n):
+        raise ValueError(f"{name}: scene map shapes do not match m / n")
+    if seg is not None:
+        eoff, S = seg
+        if not eoff.is_cuda or eoff.dtype != torch.int32 or not eoff.is_contiguous() or eoff.numel() != S + 1:
+            raise TypeError(f"{name}: eoff must be a contiguous int32 [S + 1] CUDA tensor")
+    return E, m, n
+
+
+def _grad_args(dloss, dP, dX, n, tot=None):
+    return ((dloss, "dloss", None), (dP, "dP", 12), (dX, "dX", n)) + (() if tot is None else ((tot, "tot", None),))
 
 
 def esfm_part_rows(E):
@@ -1215,11 +1250,7 @@ def esfm_part_rows(E):
 
 
 def esfm_fwd(cam, pt, vals, P, X, margin, hinge_w, hinge, part):
-    E, n = cam.shape[0], X.shape[1]
-    _i32vec(cam, "cam"), _i32vec(pt, "pt")
-    _req(vals, "vals", 2), _req(P, "P", 12), _req(X, "pts3D", n)
-    if X.shape[0] != 4 or pt.shape[0] != E or vals.shape[0] != E:
-        raise ValueError("esfm_fwd: expected pts3D [4, n] and E-long cam / pt / values")
+    E, _, n = _edge_args("esfm_fwd", cam, pt, vals, P, X)
     st = lib().gasfm_esfm_fwd(_p(cam), _p(pt), _p(vals), E, _p(P), _p(X), n, margin, hinge_w, int(hinge), _p(part),
                               _stream(X))
     check(st, "gasfm_esfm_fwd")
@@ -1228,32 +1259,107 @@ def esfm_fwd(cam, pt, vals, P, X, margin, hinge_w, hinge, part):
 def esfm_bwd(cptr, pptr, perm, cam, pt, vals, P, X, margin, hinge_w, hinge, equalize, valid_only, dloss, tot, dP,
              dX, E_norm=None):
     """E_norm: the edge count of the mean (default the local E; the global count on a sharded scene)."""
-    E, n, m = cam.shape[0], X.shape[1], P.shape[0]
+    E, m, n = _edge_args("esfm_bwd", cam, pt, vals, P, X, csr=(cptr, pptr, perm),
+                         f32=_grad_args(dloss, dP, dX, X.shape[-1], tot))
     E_norm = E if E_norm is None else int(E_norm)
-    for t, name in ((cptr, "cam_ptr"), (pptr, "pt_ptr"), (cam, "cam"), (pt, "pt")):
-        _i32vec(t, name)
-    if perm is not None:
-        _i32vec(perm, "perm")
-    if cptr.shape[0] != m + 1 or pptr.shape[0] != n + 1 or (perm is not None and perm.shape[0] != E):
-        raise ValueError("esfm_bwd: CSR shapes do not match m / n / E")
-    _req(dP, "dP", 12), _req(dX, "dX", n)
-    st = lib().gasfm_esfm_bwd(_p(cptr), m, _p(pptr), _p(perm) if perm is not None else None, _p(cam), _p(pt),
-                              _p(vals), E, E_norm, _p(P), _p(X), n, margin, hinge_w, int(hinge), int(equalize),
-                              int(valid_only), _p(dloss), _p(tot), _p(dP), _p(dX), _stream(X))
+    st = lib().gasfm_esfm_bwd(_p(cptr), m, _p(pptr), _p(perm), _p(cam), _p(pt), _p(vals), E, E_norm, _p(P), _p(X), n,
+                              margin, hinge_w, int(hinge), int(equalize), int(valid_only), _p(dloss), _p(tot), _p(dP),
+                              _p(dX), _stream(X))
     check(st, "gasfm_esfm_bwd")
+
+
+def esfm_seg_fwd(cam, pt, vals, eoff, weight, P, X, margin, hinge_w, hinge):
+    """Union-batch ESFMLoss forward (gasfm_esfm_seg_fwd): (loss [1], tot [S, 2])."""
+    S = int(weight.numel())
+    _, _, n = _edge_args("esfm_seg_fwd", cam, pt, vals, P, X, seg=(eoff, S), f32=((weight, "weight", None),))
+    dev = X.device
+    part = torch.empty((lib().gasfm_esfm_seg_part_rows(S), 2), dtype=torch.float32, device=dev)
+    tot = torch.empty((S, 2), dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    st = lib().gasfm_esfm_seg_fwd(_p(cam), _p(pt), _p(vals), _p(eoff), S, _p(weight), _p(P), _p(X), n, margin, hinge_w,
+                                  int(hinge), _p(part), _p(tot), _p(loss), _stream(X))
+    check(st, "gasfm_esfm_seg_fwd")
+    return loss, tot
+
+
+def esfm_seg_bwd(cptr, pptr, perm, cam, pt, vals, eoff, scene_of_cam, scene_of_pt, weight, P, X, margin, hinge_w,
+                 hinge, equalize, valid_only, dloss, tot, dP, dX):
+    """Union-batch ESFMLoss backward (gasfm_esfm_seg_bwd) into dP [m, 12] and dX [4, n]."""
+    S = int(weight.numel())
+    _, m, n = _edge_args("esfm_seg_bwd", cam, pt, vals, P, X, csr=(cptr, pptr, perm), seg=(eoff, S),
+                         scene_of=(scene_of_cam, scene_of_pt),
+                         f32=((weight, "weight", None),) + _grad_args(dloss, dP, dX, X.shape[-1], tot))
+    st = lib().gasfm_esfm_seg_bwd(_p(cptr), m, _p(pptr), _p(perm), _p(cam), _p(pt), _p(vals), _p(eoff), S,
+                                  _p(scene_of_cam), _p(scene_of_pt), _p(weight), _p(P), _p(X), n, margin, hinge_w,
+                                  int(hinge), int(equalize), int(valid_only), _p(dloss), _p(tot), _p(dP), _p(dX),
+                                  _stream(X))
+    check(st, "gasfm_esfm_seg_bwd")
+
+
+def ose_fwd(cam, pt, vals, P, X, w_reg):
+    """Per-workgroup sums [rows, 1] of the OSE + exp-depth terms (finish with colsum)."""
+    E, _, n = _edge_args("ose_fwd", cam, pt, vals, P, X)
+    part = torch.empty((lib().gasfm_ose_part_rows(E), 1), dtype=torch.float32, device=X.device)
+    st = lib().gasfm_ose_fwd(_p(cam), _p(pt), _p(vals), E, _p(P), _p(X), n, w_reg, _p(part), _stream(X))
+    check(st, "gasfm_ose_fwd")
+    return part
+
+
+def ose_bwd(cptr, pptr, perm, cam, pt, vals, P, X, w_reg, dloss, dP, dX):
+    E, m, n = _edge_args("ose_bwd", cam, pt, vals, P, X, csr=(cptr, pptr, perm),
+                         f32=_grad_args(dloss, dP, dX, X.shape[-1]))
+    st = lib().gasfm_ose_bwd(_p(cptr), m, _p(pptr), _p(perm), _p(cam), _p(pt), _p(vals), E, _p(P), _p(X), n, w_reg,
+                             _p(dloss), _p(dP), _p(dX), _stream(X))
+    check(st, "gasfm_ose_bwd")
+
+
+def ose_seg_fwd(cam, pt, vals, eoff, weight, P, X, w_reg):
+    """Union-batch OSE loss forward (gasfm_ose_seg_fwd): (loss [1], tot [S])."""
+    S = int(weight.numel())
+    _, _, n = _edge_args("ose_seg_fwd", cam, pt, vals, P, X, seg=(eoff, S), f32=((weight, "weight", None),))
+    dev = X.device
+    part = torch.empty(lib().gasfm_ose_seg_part_rows(S), dtype=torch.float32, device=dev)
+    tot = torch.empty(S, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    st = lib().gasfm_ose_seg_fwd(_p(cam), _p(pt), _p(vals), _p(eoff), S, _p(weight), _p(P), _p(X), n, w_reg, _p(part),
+                                 _p(tot), _p(loss), _stream(X))
+    check(st, "gasfm_ose_seg_fwd")
+    return loss, tot
+
+
+def ose_seg_bwd(cptr, pptr, perm, cam, pt, vals, eoff, scene_of_cam, scene_of_pt, weight, P, X, w_reg, dloss, dP, dX):
+    """Union-batch OSE loss backward (gasfm_ose_seg_bwd) into dP [m, 12] and dX [4, n]."""
+    S = int(weight.numel())
+    _, m, n = _edge_args("ose_seg_bwd", cam, pt, vals, P, X, csr=(cptr, pptr, perm), seg=(eoff, S),
+                         scene_of=(scene_of_cam, scene_of_pt),
+                         f32=((weight, "weight", None),) + _grad_args(dloss, dP, dX, X.shape[-1]))
+    st = lib().gasfm_ose_seg_bwd(_p(cptr), m, _p(pptr), _p(perm), _p(cam), _p(pt), _p(vals), _p(eoff), S,
+                                 _p(scene_of_cam), _p(scene_of_pt), _p(weight), _p(P), _p(X), n, w_reg, _p(dloss),
+                                 _p(dP), _p(dX), _stream(X))
+    check(st, "gasfm_ose_seg_bwd")
 
 
 def reproj_error(cam, pt, xy, P, X, err=None):
     """Per-workgroup (sum, count) of the non-NaN reprojection errors (and err[e] if given)."""
-    E, n = cam.shape[0], X.shape[1]
-    _i32vec(cam, "cam"), _i32vec(pt, "pt")
-    _req(xy, "xy", 2), _req(P, "P", 12), _req(X, "pts3D", n)
-    if X.shape[0] != 4 or pt.shape[0] != E or xy.shape[0] != E or (err is not None and err.shape[0] != E):
+    E, _, n = _edge_args("reproj_error", cam, pt, xy, P, X, f32=() if err is None else ((err, "err", None),))
+    if err is not None and err.shape[0] != E:
         raise ValueError("reproj_error: expected pts3D [4, n] and E-long cam / pt / xy / err")
     part = torch.empty((esfm_part_rows(E), 2), dtype=torch.float32, device=X.device)
     st = lib().gasfm_reproj_error(_p(cam), _p(pt), _p(xy), E, _p(P), _p(X), n, _p(err), _p(part), _stream(X))
     check(st, "gasfm_reproj_error")
     return part
+
+
+def reproj_error_seg(cam, pt, xy, eoff, S, P, X):
+    """Per scene of a union batch: tot [S, 2] = (sum of the non-NaN reprojection errors, count)."""
+    _, _, n = _edge_args("reproj_error_seg", cam, pt, xy, P, X, seg=(eoff, S))
+    dev = X.device
+    part = torch.empty((lib().gasfm_esfm_seg_part_rows(S), 2), dtype=torch.float32, device=dev)
+    tot = torch.empty((S, 2), dtype=torch.float32, device=dev)
+    st = lib().gasfm_reproj_error_seg(_p(cam), _p(pt), _p(xy), _p(eoff), S, _p(P), _p(X), n, _p(part), _p(tot),
+                                      _stream(X))
+    check(st, "gasfm_reproj_error_seg")
+    return tot
 
 
 def depth_stats(cam, pt, cam_ptr, pt_ptr, perm, P, X, margin, depth=None):
@@ -1284,101 +1390,6 @@ def depth_stats(cam, pt, cam_ptr, pt_ptr, perm, P, X, margin, depth=None):
     return cam_neg, pt_neg, stats
 
 
-def _seg_args(eoff, S, name):
-    if eoff.dtype != torch.int32 or not eoff.is_contiguous() or eoff.numel() != S + 1:
-        raise TypeError(f"{name}: eoff must be a contiguous int32 [S + 1] tensor")
-
-
-def esfm_seg_fwd(cam, pt, vals, eoff, weight, P, X, margin, hinge_w, hinge):
-    """Union-batch ESFMLoss forward (gasfm_esfm_seg_fwd): (loss [1], tot [S, 2])."""
-    S = int(weight.numel())
-    _seg_args(eoff, S, "esfm_seg_fwd")
-    n = X.shape[1]
-    if X.shape[0] != 4 or cam.shape != pt.shape or vals.shape != (cam.shape[0], 2):
-        raise ValueError("esfm_seg_fwd: expected pts3D [4, n] and E-long cam / pt / values")
-    dev = X.device
-    part = torch.empty((lib().gasfm_esfm_seg_part_rows(S), 2), dtype=torch.float32, device=dev)
-    tot = torch.empty((S, 2), dtype=torch.float32, device=dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    st = lib().gasfm_esfm_seg_fwd(_p(cam), _p(pt), _p(vals), _p(eoff), S, _p(weight), _p(P), _p(X), n, margin, hinge_w,
-                                  int(hinge), _p(part), _p(tot), _p(loss), _stream(X))
-    check(st, "gasfm_esfm_seg_fwd")
-    return loss, tot
-
-
-def esfm_seg_bwd(cptr, pptr, perm, cam, pt, vals, eoff, scene_of_cam, scene_of_pt, weight, P, X, margin, hinge_w,
-                 hinge, equalize, valid_only, dloss, tot, dP, dX):
-    """Union-batch ESFMLoss backward (gasfm_esfm_seg_bwd) into dP [m, 12] and dX [4, n]."""
-    S = int(weight.numel())
-    _seg_args(eoff, S, "esfm_seg_bwd")
-    m, n = P.shape[0], X.shape[1]
-    if cptr.numel() != m + 1 or pptr.numel() != n + 1 or scene_of_cam.numel() != m or scene_of_pt.numel() != n:
-        raise ValueError("esfm_seg_bwd: CSR / scene map shapes do not match m / n")
-    st = lib().gasfm_esfm_seg_bwd(_p(cptr), m, _p(pptr), _p(perm), _p(cam), _p(pt), _p(vals), _p(eoff), S,
-                                  _p(scene_of_cam), _p(scene_of_pt), _p(weight), _p(P), _p(X), n, margin, hinge_w,
-                                  int(hinge), int(equalize), int(valid_only), _p(dloss), _p(tot), _p(dP), _p(dX),
-                                  _stream(X))
-    check(st, "gasfm_esfm_seg_bwd")
-
-
-# ------------------------------------------- ExpDepthRegularizedOSELoss (ose_loss.hip)
-def ose_fwd(cam, pt, vals, P, X, w_reg):
-    """Per-workgroup sums [rows, 1] of the OSE + exp-depth terms (finish with colsum)."""
-    E, n = cam.shape[0], X.shape[1]
-    _i32vec(cam, "cam"), _i32vec(pt, "pt")
-    _req(vals, "vals", 2), _req(P, "P", 12), _req(X, "pts3D", n)
-    if X.shape[0] != 4 or pt.shape[0] != E or vals.shape[0] != E:
-        raise ValueError("ose_fwd: expected pts3D [4, n] and E-long cam / pt / values")
-    part = torch.empty((lib().gasfm_ose_part_rows(E), 1), dtype=torch.float32, device=X.device)
-    st = lib().gasfm_ose_fwd(_p(cam), _p(pt), _p(vals), E, _p(P), _p(X), n, w_reg, _p(part), _stream(X))
-    check(st, "gasfm_ose_fwd")
-    return part
-
-
-def ose_bwd(cptr, pptr, perm, cam, pt, vals, P, X, w_reg, dloss, dP, dX):
-    E, n, m = cam.shape[0], X.shape[1], P.shape[0]
-    for t, name in ((cptr, "cam_ptr"), (pptr, "pt_ptr"), (cam, "cam"), (pt, "pt")):
-        _i32vec(t, name)
-    if perm is not None:
-        _i32vec(perm, "perm")
-    if cptr.shape[0] != m + 1 or pptr.shape[0] != n + 1 or (perm is not None and perm.shape[0] != E):
-        raise ValueError("ose_bwd: CSR shapes do not match m / n / E")
-    _req(vals, "vals", 2), _req(dloss, "dloss"), _req(dP, "dP", 12), _req(dX, "dX", n)
-    st = lib().gasfm_ose_bwd(_p(cptr), m, _p(pptr), _p(perm), _p(cam), _p(pt), _p(vals), E, _p(P), _p(X), n, w_reg,
-                             _p(dloss), _p(dP), _p(dX), _stream(X))
-    check(st, "gasfm_ose_bwd")
-
-
-def ose_seg_fwd(cam, pt, vals, eoff, weight, P, X, w_reg):
-    """Union-batch OSE loss forward (gasfm_ose_seg_fwd): (loss [1], tot [S])."""
-    S = int(weight.numel())
-    _seg_args(eoff, S, "ose_seg_fwd")
-    n = X.shape[1]
-    if X.shape[0] != 4 or cam.shape != pt.shape or vals.shape != (cam.shape[0], 2):
-        raise ValueError("ose_seg_fwd: expected pts3D [4, n] and E-long cam / pt / values")
-    dev = X.device
-    part = torch.empty(lib().gasfm_ose_seg_part_rows(S), dtype=torch.float32, device=dev)
-    tot = torch.empty(S, dtype=torch.float32, device=dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    st = lib().gasfm_ose_seg_fwd(_p(cam), _p(pt), _p(vals), _p(eoff), S, _p(weight), _p(P), _p(X), n, w_reg, _p(part),
-                                 _p(tot), _p(loss), _stream(X))
-    check(st, "gasfm_ose_seg_fwd")
-    return loss, tot
-
-
-def ose_seg_bwd(cptr, pptr, perm, cam, pt, vals, eoff, scene_of_cam, scene_of_pt, weight, P, X, w_reg, dloss, dP, dX):
-    """Union-batch OSE loss backward (gasfm_ose_seg_bwd) into dP [m, 12] and dX [4, n]."""
-    S = int(weight.numel())
-    _seg_args(eoff, S, "ose_seg_bwd")
-    m, n = P.shape[0], X.shape[1]
-    if cptr.numel() != m + 1 or pptr.numel() != n + 1 or scene_of_cam.numel() != m or scene_of_pt.numel() != n:
-        raise ValueError("ose_seg_bwd: CSR / scene map shapes do not match m / n")
-    st = lib().gasfm_ose_seg_bwd(_p(cptr), m, _p(pptr), _p(perm), _p(cam), _p(pt), _p(vals), _p(eoff), S,
-                                 _p(scene_of_cam), _p(scene_of_pt), _p(weight), _p(P), _p(X), n, w_reg, _p(dloss),
-                                 _p(dP), _p(dX), _stream(X))
-    check(st, "gasfm_ose_seg_bwd")
-
-
 # ------------------------------------------- DirectDepthLoss (depth_loss.hip)
 def _depth_args(a, b, name):
     _req(a, "depths"), _req(b, "depth targets")
@@ -1406,18 +1417,6 @@ def depth_loss_bwd(a, b, sums, tot, l2, dloss):
                                     _stream(a))
     check(st, "gasfm_depth_loss_bwd")
     return da
-
-
-def reproj_error_seg(cam, pt, xy, eoff, S, P, X):
-    """Per scene of a union batch: tot [S, 2] = (sum of the non-NaN reprojection errors, count)."""
-    _seg_args(eoff, S, "reproj_error_seg")
-    dev = X.device
-    part = torch.empty((lib().gasfm_esfm_seg_part_rows(S), 2), dtype=torch.float32, device=dev)
-    tot = torch.empty((S, 2), dtype=torch.float32, device=dev)
-    st = lib().gasfm_reproj_error_seg(_p(cam), _p(pt), _p(xy), _p(eoff), S, _p(P), _p(X), X.shape[1], _p(part),
-                                      _p(tot), _stream(X))
-    check(st, "gasfm_reproj_error_seg")
-    return tot
 
 
 class UnionScene(ctypes.Structure):

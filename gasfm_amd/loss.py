@@ -28,6 +28,25 @@ import torch
 from . import _native
 
 
+def _check_projection_inputs(name, Ps, pts3D):
+    for t, tname in ((Ps, "Ps_norm"), (pts3D, "pts3D")):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise TypeError(f"{name}: {tname} must be a float32 CUDA tensor (no CPU fallback)")
+    if Ps.dim() != 3 or tuple(Ps.shape[1:]) != (3, 4) or pts3D.dim() != 2 or pts3D.shape[0] != 4:
+        raise ValueError(f"{name}: expected Ps_norm [m, 3, 4] and pts3D [4, n], got {tuple(Ps.shape)}, "
+                         f"{tuple(pts3D.shape)}")
+
+
+def _flat_inputs(Ps, pts3D):
+    """(P [m, 12], X [4, n]) contiguous, as the per-edge kernels read them."""
+    return Ps.reshape(Ps.shape[0], 12).contiguous(), pts3D.contiguous()
+
+
+def _grad_buffers(dloss, P, X):
+    """(dloss [1] float32, dP, dX) for a per-edge backward; it returns dP.view(-1, 3, 4), dX."""
+    return dloss.reshape(1).to(torch.float32).contiguous(), torch.empty_like(P), torch.empty_like(X)
+
+
 class ESFMLossFn(torch.autograd.Function):
     """(Ps [m, 3, 4], pts3D [4, n]) -> mean over the edges of the per-edge loss term."""
 
@@ -39,9 +58,7 @@ class ESFMLossFn(torch.autograd.Function):
         edge count; backward: dpts3D is rank-local and complete, dPs is summed over the ranks."""
         margin, hinge_w, hinge, equalize, valid_only = conf
         cam, pt = edges
-        m = Ps.shape[0]
-        P = Ps.reshape(m, 12).contiguous()
-        X = pts3D.contiguous()
+        P, X = _flat_inputs(Ps, pts3D)
         part = torch.empty((_native.esfm_part_rows(cam.shape[0]), 2), dtype=torch.float32, device=X.device)
         _native.esfm_fwd(cam, pt, vals, P, X, margin, hinge_w, hinge, part)
         tot = _native.colsum(part)  # (sum of terms, #valid-depth)
@@ -57,15 +74,14 @@ class ESFMLossFn(torch.autograd.Function):
     def backward(ctx, dloss):
         P, X, cam, pt, vals, cam_ptr, pt_ptr, pt_perm, tot = ctx.saved_tensors
         margin, hinge_w, hinge, equalize, valid_only = ctx.conf
-        dP, dX = torch.empty_like(P), torch.empty_like(X)
-        dloss = dloss.reshape(1).to(torch.float32).contiguous()
+        dloss, dP, dX = _grad_buffers(dloss, P, X)
         # E_norm = the global edge count on a sharded scene: the un-equalized terms and the equalized
         # (normalize(G) / E) branch both divide by it, as loss_functions.py:110 divides by sum(valid_pts)
         _native.esfm_bwd(cam_ptr, pt_ptr, pt_perm, cam, pt, vals, P, X, margin, hinge_w, hinge, equalize, valid_only,
                          dloss, tot, dP, dX, E_norm=ctx.E)
         if ctx.shard is not None:
             ctx.shard.all_reduce_(dP)
-        return dP.view(-1, 3, 4), dX, None, None, None, None, None, None, None, None
+        return (dP.view(-1, 3, 4), dX) + (None,) * 8
 
 
 def scene_csr(data):
@@ -124,12 +140,7 @@ class ESFMLoss(torch.nn.Module):
 
     def forward(self, pred_dict, data, epoch=None):
         Ps, pts3D = pred_dict["Ps_norm"], pred_dict["pts3D"]
-        for t, name, shape in ((Ps, "Ps_norm", (3, 4)), (pts3D, "pts3D", None)):
-            if not t.is_cuda or t.dtype != torch.float32:
-                raise TypeError(f"ESFMLoss: {name} must be a float32 CUDA tensor (no CPU fallback)")
-        if Ps.dim() != 3 or tuple(Ps.shape[1:]) != (3, 4) or pts3D.dim() != 2 or pts3D.shape[0] != 4:
-            raise ValueError(f"ESFMLoss: expected Ps_norm [m, 3, 4] and pts3D [4, n], got {tuple(Ps.shape)}, "
-                             f"{tuple(pts3D.shape)}")
+        _check_projection_inputs("ESFMLoss", Ps, pts3D)
         edges, vals, cam_ptr, pt_ptr, pt_perm = _edge_tensors(data)
         if edges[0].shape[0] == 0:
             raise ValueError("ESFMLoss: no valid observations (the reference's mean would be NaN)")
@@ -141,15 +152,6 @@ class ESFMLoss(torch.nn.Module):
                                 E_global)
 
 
-def _check_projection_inputs(name, Ps, pts3D):
-    for t, tname in ((Ps, "Ps_norm"), (pts3D, "pts3D")):
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise TypeError(f"{name}: {tname} must be a float32 CUDA tensor (no CPU fallback)")
-    if Ps.dim() != 3 or tuple(Ps.shape[1:]) != (3, 4) or pts3D.dim() != 2 or pts3D.shape[0] != 4:
-        raise ValueError(f"{name}: expected Ps_norm [m, 3, 4] and pts3D [4, n], got {tuple(Ps.shape)}, "
-                         f"{tuple(pts3D.shape)}")
-
-
 class OSELossFn(torch.autograd.Function):
     """(Ps [m, 3, 4], pts3D [4, n]) -> mean over the edges of ||y_xy - y_z m_e|| + w_reg exp(-y_z)
     (csrc/ose_loss.hip)."""
@@ -157,8 +159,7 @@ class OSELossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, Ps, pts3D, edges, vals, cam_ptr, pt_ptr, pt_perm, w_reg):
         cam, pt = edges
-        P = Ps.reshape(Ps.shape[0], 12).contiguous()
-        X = pts3D.contiguous()
+        P, X = _flat_inputs(Ps, pts3D)
         tot = _native.colsum(_native.ose_fwd(cam, pt, vals, P, X, w_reg))
         ctx.save_for_backward(P, X, cam, pt, vals, cam_ptr, pt_ptr, pt_perm)
         ctx.w_reg = w_reg
@@ -167,10 +168,9 @@ class OSELossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss):
         P, X, cam, pt, vals, cam_ptr, pt_ptr, pt_perm = ctx.saved_tensors
-        dP, dX = torch.empty_like(P), torch.empty_like(X)
-        dloss = dloss.reshape(1).to(torch.float32).contiguous()
+        dloss, dP, dX = _grad_buffers(dloss, P, X)
         _native.ose_bwd(cam_ptr, pt_ptr, pt_perm, cam, pt, vals, P, X, ctx.w_reg, dloss, dP, dX)
-        return dP.view(-1, 3, 4), dX, None, None, None, None, None, None
+        return (dP.view(-1, 3, 4), dX) + (None,) * 6
 
 
 class ExpDepthRegularizedOSELoss(torch.nn.Module):

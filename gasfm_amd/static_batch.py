@@ -51,6 +51,7 @@ from . import _native
 from .attention import DEFAULT_MAX_PIECE, AttnPlan
 from .batch import _scene_arrays
 from .graph_step import gc_paused
+from .loss import ESFMLoss, ExpDepthRegularizedOSELoss, _flat_inputs, _grad_buffers
 from .model import EdgeIndex, require_gasfm
 from .scene import MIN_N_POINTS_PER_VIEW, MIN_N_VIEWS_PER_POINT, AxialAggregationGraphWrapper, SparseMat
 
@@ -555,65 +556,38 @@ class StaticBatch:
 
 
 class BatchLossFn(torch.autograd.Function):
-    """sum over the real scenes of ESFMLoss(pred, scene) on a StaticBatch (gasfm_esfm_seg_fwd / _bwd):
-    the eager step's ``sum(lossf(p, d) for ...)`` with fixed launch geometry."""
+    """sum over the real scenes of a per-edge loss on a StaticBatch (a gasfm_*_seg_fwd / _bwd pair): the
+    eager step's ``sum(lossf(p, d) for ...)`` with fixed launch geometry.  ``fwd`` / ``bwd`` are the
+    loss's _native wrappers, ``params`` its parameter tuple (the forward takes the first ``n_fwd``),
+    ``tot_in_bwd`` whether the backward reads the forward's per-scene totals."""
 
     @staticmethod
-    def forward(ctx, Ps, pts3D, sb, conf):
-        margin, hinge_w, hinge, equalize, valid_only = conf
-        P = Ps.reshape(Ps.shape[0], 12).contiguous()
-        X = pts3D.contiguous()
-        loss, tot = _native.esfm_seg_fwd(sb.cam32, sb.pt32, sb.values_loss, sb.eoff, sb.weight, P, X, margin,
-                                         hinge_w, hinge)
+    def forward(ctx, Ps, pts3D, sb, fwd, bwd, params, n_fwd, tot_in_bwd):
+        P, X = _flat_inputs(Ps, pts3D)
+        loss, tot = fwd(sb.cam32, sb.pt32, sb.values_loss, sb.eoff, sb.weight, P, X, *params[:n_fwd])
         ctx.save_for_backward(P, X, tot)
-        ctx.sb, ctx.conf = sb, conf
+        ctx.sb, ctx.bwd, ctx.params, ctx.tot_in_bwd = sb, bwd, params, tot_in_bwd
         return loss.view(())
 
     @staticmethod
     def backward(ctx, dloss):
         P, X, tot = ctx.saved_tensors
         sb = ctx.sb
-        margin, hinge_w, hinge, equalize, valid_only = ctx.conf
-        dP, dX = torch.empty_like(P), torch.empty_like(X)
-        dloss = dloss.reshape(1).to(torch.float32).contiguous()
-        _native.esfm_seg_bwd(sb.cam_ptr, sb.pt_ptr, sb.perm, sb.cam32, sb.pt32, sb.values_loss, sb.eoff, sb.soc32,
-                             sb.sop32, sb.weight, P, X, margin, hinge_w, hinge, equalize, valid_only, dloss, tot, dP,
-                             dX)
-        return dP.view(-1, 3, 4), dX, None, None
-
-
-class BatchOSELossFn(torch.autograd.Function):
-    """sum over the real scenes of ExpDepthRegularizedOSELoss(pred, scene) on a StaticBatch
-    (gasfm_ose_seg_fwd / _bwd), as BatchLossFn."""
-
-    @staticmethod
-    def forward(ctx, Ps, pts3D, sb, w_reg):
-        P = Ps.reshape(Ps.shape[0], 12).contiguous()
-        X = pts3D.contiguous()
-        loss, _ = _native.ose_seg_fwd(sb.cam32, sb.pt32, sb.values_loss, sb.eoff, sb.weight, P, X, w_reg)
-        ctx.save_for_backward(P, X)
-        ctx.sb, ctx.w_reg = sb, w_reg
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, dloss):
-        P, X = ctx.saved_tensors
-        sb = ctx.sb
-        dP, dX = torch.empty_like(P), torch.empty_like(X)
-        dloss = dloss.reshape(1).to(torch.float32).contiguous()
-        _native.ose_seg_bwd(sb.cam_ptr, sb.pt_ptr, sb.perm, sb.cam32, sb.pt32, sb.values_loss, sb.eoff, sb.soc32,
-                            sb.sop32, sb.weight, P, X, ctx.w_reg, dloss, dP, dX)
-        return dP.view(-1, 3, 4), dX, None, None
+        dloss, dP, dX = _grad_buffers(dloss, P, X)
+        ctx.bwd(sb.cam_ptr, sb.pt_ptr, sb.perm, sb.cam32, sb.pt32, sb.values_loss, sb.eoff, sb.soc32, sb.sop32,
+                sb.weight, P, X, *ctx.params, dloss, *((tot,) if ctx.tot_in_bwd else ()), dP, dX)
+        return (dP.view(-1, 3, 4), dX) + (None,) * 6
 
 
 def batch_loss(pred, sb, lossf):
-    from .loss import ESFMLoss, ExpDepthRegularizedOSELoss
     if isinstance(lossf, ESFMLoss):
-        return BatchLossFn.apply(pred["Ps_norm"], pred["pts3D"], sb, lossf.kernel_conf())
-    if isinstance(lossf, ExpDepthRegularizedOSELoss):
-        return BatchOSELossFn.apply(pred["Ps_norm"], pred["pts3D"], sb, float(lossf.depth_regul_weight))
-    raise TypeError(f"batch_loss: no union-batch form of {type(lossf).__name__} (ESFMLoss and "
-                    "ExpDepthRegularizedOSELoss have one)")
+        kernels = (_native.esfm_seg_fwd, _native.esfm_seg_bwd, lossf.kernel_conf(), 3, True)
+    elif isinstance(lossf, ExpDepthRegularizedOSELoss):
+        kernels = (_native.ose_seg_fwd, _native.ose_seg_bwd, (float(lossf.depth_regul_weight),), 1, False)
+    else:
+        raise TypeError(f"batch_loss: no union-batch form of {type(lossf).__name__} (ESFMLoss and "
+                        "ExpDepthRegularizedOSELoss have one)")
+    return BatchLossFn.apply(pred["Ps_norm"], pred["pts3D"], sb, *kernels)
 
 
 def batch_repro_errors(pred, sb):

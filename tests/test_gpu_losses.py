@@ -1,7 +1,8 @@
 """The HIP ExpDepthRegularizedOSELoss (csrc/ose_loss.hip), its union-batch / captured-step form
 (gasfm_ose_seg_fwd / _bwd, static_batch.batch_loss, StaticTrainer) and DirectDepthLoss
 (csrc/depth_loss.hip) against the fp64 per-edge restatements of tests/test_losses_cpu.py, which that
-file pins to the reference's dense formulation.
+file pins to the reference's dense formulation; and the per-edge scaffold the ESFM and OSE kernels
+share (csrc/edge_loss.hpp) on hand-made plans.
 
 Tolerance, as tests/test_gpu_esfm_loss.py (fp32 kernel vs fp64 reference):
     loss:   |got - ref| <= 1e-5 |ref|
@@ -15,11 +16,11 @@ import pytest
 import torch
 
 import gasfm_amd
-from gasfm_amd import static_batch, synthetic
+from gasfm_amd import _native, static_batch, synthetic
 from gasfm_amd.loss import DirectDepthLoss, ExpDepthRegularizedOSELoss
 from gasfm_amd.scene import SparseMat
 
-from test_gpu_esfm_loss import close, predictions
+from test_gpu_esfm_loss import VARIANTS, close, oracle_run, predictions
 from test_gpu_static_batch import _eager, _scenes
 from test_gpu_train_step import conf_with_loss
 from test_losses_cpu import depth_loss_edges, ose_loss_edges
@@ -111,7 +112,161 @@ def test_ose_edge_cases(device):
     np.testing.assert_allclose(dX0[:, 0].cpu().numpy(), dX1[:, 0].cpu().numpy(), rtol=1e-6, atol=1e-9)
 
 
-def test_ose_input_checks(device):
+# ---------------------------------------------------------------- the shared per-edge scaffold
+HAND_M, HAND_N, HAND_DLOSS, HAND_WREG = 4, 259, 0.75, 0.1
+HAND_WEIGHTS = (1.0, 0.0, 0.5)  # of the three copies of a plan in the segmented form
+HAND_ESFM = VARIANTS[0]  # (margin, equalize, valid_only, hinge, hinge_w): equalize + valid_only
+# Points seen by each of the 4 cameras, edges in camera-major order.  "perm": 0, 1, 257 and 64 edges
+# (an empty range, a single lane, one lap past the 256-thread workgroup, exactly one wave); edge 0
+# sees point 5, so the point CSR needs a non-identity perm.  "sorted": camera-major edges that are
+# also point-sorted (perm = None), which 259 points allow with 0, 1, 257 and 2 edges.  Both: 259
+# points = one full point workgroup + 3 threads, point 258 has no edge.
+HAND_PLANS = {"perm": [[], [5], range(257), range(194, 258)], "sorted": [[], [0], range(257), [256, 257]]}
+
+
+def _hand_case(name, seed, device):
+    counts = [len(p) for p in HAND_PLANS[name]]
+    cam = np.repeat(np.arange(HAND_M), counts)
+    pt = np.concatenate([np.asarray(p, dtype=np.int64) for p in HAND_PLANS[name]])
+    perm = np.argsort(pt, kind="stable")
+    assert (name == "sorted") == bool((perm == np.arange(len(pt))).all())
+    cam_ptr = np.concatenate([[0], np.cumsum(counts)])
+    pt_ptr = np.concatenate([[0], np.cumsum(np.bincount(pt, minlength=HAND_N))])
+    assert pt_ptr[-1] == pt_ptr[-2] == len(pt)
+    Ps, X = predictions(HAND_M, HAND_N, seed, "cpu")
+    g = torch.Generator().manual_seed(seed + 1)
+    vals = (0.5 * torch.randn((len(pt), 2), generator=g, dtype=torch.float64)).float()
+    cam_t, pt_t = torch.from_numpy(cam), torch.from_numpy(pt)
+    # the fp64 reference stays away from the kinks: no depth within 1e-3 of the margin (fp32 roundoff
+    # of y_z is ~1e-6), both sides of it present, no residual below 1e-3
+    y = torch.einsum("eij,je->ei", Ps[cam_t], X[:, pt_t])
+    margin, eq, vo, hinge, w = HAND_ESFM
+    pos = y[:, 2] >= margin
+    assert float((y[:, 2] - margin).abs().min()) > 1e-3 and pos.any() and not pos.all()
+    assert float((y[pos, :2] / y[pos, 2:3] - vals[pos]).norm(dim=1).min()) > 1e-3
+    assert float((y[:, :2] - y[:, 2:3] * vals).norm(dim=1).min()) > 1e-3
+    # per scene weight: the equalized gradient is normalised per edge, so it is not linear in the weight
+    refs = {}
+    for sw in HAND_WEIGHTS:
+        if sw != 0:
+            refs["esfm", sw] = oracle_run(Ps, X, cam_t, pt_t, vals, HAND_ESFM, dloss=HAND_DLOSS * sw)
+            refs["ose", sw] = oracle_ose(Ps, X, cam_t, pt_t, vals, HAND_WREG, dloss=HAND_DLOSS * sw)
+    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=torch.int32)
+    return {"cam": i32(cam), "pt": i32(pt), "cam_ptr": i32(cam_ptr), "pt_ptr": i32(pt_ptr),
+            "perm": None if name == "sorted" else i32(perm), "vals": vals.to(device),
+            "P": Ps.float().reshape(HAND_M, 12).to(device), "X": X.float().to(device),
+            "refs": {k: tuple(t.detach() for t in v) for k, v in refs.items()}, "npos": int(pos.sum())}
+
+
+@pytest.fixture(scope="module")
+def hand_cases(device):
+    """The two hand-made plans with their fp64 autograd references, shared and left unchanged."""
+    return {"perm": _hand_case("perm", 41, device), "sorted": _hand_case("sorted", 43, device)}
+
+
+def _hand_run(loss, c, P, X, seg=None):
+    """(loss [1] or 0-d, tot, dP, dX) through the _native wrappers, dloss = HAND_DLOSS; ``seg`` =
+    (eoff, scene_of_cam, scene_of_pt, weight) runs the union-batch pair."""
+    margin, eq, vo, hinge, w = HAND_ESFM
+    dP, dX = torch.full_like(P, 7.0), torch.full_like(X, 7.0)
+    dloss = torch.full((1,), HAND_DLOSS, device=P.device)
+    edges, csr, E = (c["cam"], c["pt"], c["vals"]), (c["cam_ptr"], c["pt_ptr"], c["perm"]), c["cam"].shape[0]
+    if seg is None and loss == "esfm":
+        part = torch.empty((_native.esfm_part_rows(E), 2), device=P.device)
+        _native.esfm_fwd(*edges, P, X, margin, w, hinge, part)
+        tot = _native.colsum(part)
+        _native.esfm_bwd(*csr, *edges, P, X, margin, w, hinge, eq, vo, dloss, tot, dP, dX)
+        return tot[0] / E, tot, dP, dX
+    if seg is None:
+        tot = _native.colsum(_native.ose_fwd(*edges, P, X, HAND_WREG))
+        _native.ose_bwd(*csr, *edges, P, X, HAND_WREG, dloss, dP, dX)
+        return tot[0] / E, tot, dP, dX
+    eoff, soc, sop, weight = seg
+    if loss == "esfm":
+        out, tot = _native.esfm_seg_fwd(*edges, eoff, weight, P, X, margin, w, hinge)
+        _native.esfm_seg_bwd(*csr, *edges, eoff, soc, sop, weight, P, X, margin, w, hinge, eq, vo, dloss, tot, dP, dX)
+    else:
+        out, tot = _native.ose_seg_fwd(*edges, eoff, weight, P, X, HAND_WREG)
+        _native.ose_seg_bwd(*csr, *edges, eoff, soc, sop, weight, P, X, HAND_WREG, dloss, dP, dX)
+    return out[0], tot, dP, dX
+
+
+def _hand_union(c, weights):
+    """len(weights) copies of a hand case as one union batch; the predictions of the weight-0 copies are NaN."""
+    S, E, dev = len(weights), c["cam"].shape[0], c["P"].device
+    rep = lambda v, step: torch.cat([v + s * step for s in range(S)])
+    ptr = lambda v: torch.cat([v[:-1] + s * E for s in range(S)] + [v.new_tensor([S * E])])
+    u = {"cam": rep(c["cam"], HAND_M), "pt": rep(c["pt"], HAND_N), "vals": c["vals"].repeat(S, 1),
+         "cam_ptr": ptr(c["cam_ptr"]), "pt_ptr": ptr(c["pt_ptr"]),
+         "perm": None if c["perm"] is None else rep(c["perm"], E)}
+    P, X = c["P"].repeat(S, 1), c["X"].repeat(1, S)
+    for s, w in enumerate(weights):
+        if w == 0:
+            P[s * HAND_M:(s + 1) * HAND_M] = float("nan")
+            X[:, s * HAND_N:(s + 1) * HAND_N] = float("nan")
+    arange = torch.arange(S, dtype=torch.int32, device=dev)
+    seg = (arange.new_tensor([s * E for s in range(S + 1)]), arange.repeat_interleave(HAND_M),
+           arange.repeat_interleave(HAND_N), torch.tensor(weights, dtype=torch.float32, device=dev))
+    return u, P, X, seg
+
+
+@pytest.mark.parametrize("form", ["flat", "segmented"])
+@pytest.mark.parametrize("loss", ["esfm", "ose"])
+def test_edge_scaffold_hand_plans_vs_fp64(device, hand_cases, loss, form):
+    """Every branch of the shared per-edge scaffold (csrc/edge_loss.hpp) at its smallest size, for a
+    two-stat term with the equalized gradient and a one-stat term: HAND_PLANS, with and without a
+    point perm, against fp64 autograd of the same per-edge formula.  Segmented: three copies with
+    weights (1, 0, 0.5); the weight-0 copy's predictions are NaN and its gradients exact zeros, the
+    total is the weighted sum of the flat losses (to the loss tolerance: 32 slices per scene against
+    2 workgroups + colsum order the sums differently), and a copy's gradients are those of
+    weight x loss (the equalized gradient is normalised per edge, so not the weight x the gradients)."""
+    for name, c in hand_cases.items():
+        rl, rP, rX = c["refs"][loss, 1.0]
+        fl, ftot, fP, fX = _hand_run(loss, c, c["P"], c["X"])
+        if form == "flat":
+            print(f"hand {loss} {name}: loss {fl.item():.9g} ref {rl.item():.9g}")
+            np.testing.assert_allclose(fl.item(), rl.item(), rtol=1e-5)
+            close(fP, rP.reshape(HAND_M, 12), "dPs")
+            close(fX, rX, "dpts3D")
+            assert float(fP[0].abs().max()) == 0.0 and float(fX[:, -1].abs().max()) == 0.0
+            if loss == "esfm":
+                assert ftot[1].item() == c["npos"]
+            continue
+        weights = HAND_WEIGHTS
+        u, P, X, seg = _hand_union(c, weights)
+        sl, stot, sP, sX = _hand_run(loss, u, P, X, seg)
+        print(f"hand {loss} {name} segmented: loss {sl.item():.9g} flat {fl.item():.9g} ref {rl.item():.9g}")
+        np.testing.assert_allclose(sl.item(), sum(weights) * rl.item(), rtol=1e-5)
+        np.testing.assert_allclose(sl.item(), sum(w * fl.item() for w in weights), rtol=1e-5)
+        for s, w in enumerate(weights):
+            gP, gX = sP[s * HAND_M:(s + 1) * HAND_M], sX[:, s * HAND_N:(s + 1) * HAND_N]
+            if w == 0:
+                assert float(gP.abs().max()) == 0.0 and float(gX.abs().max()) == 0.0
+                continue
+            close(gP, c["refs"][loss, w][1].reshape(HAND_M, 12), f"dPs scene {s}")
+            close(gX, c["refs"][loss, w][2], f"dpts3D scene {s}")
+            assert float(gP[0].abs().max()) == 0.0 and float(gX[:, -1].abs().max()) == 0.0
+            if loss == "esfm":
+                assert stot[s, 1].item() == c["npos"]
+
+
+def test_ose_input_checks(device, hand_cases):
+    # a segmented wrapper validates its index tensors; float2 reads need 8-byte aligned values
+    c = hand_cases["perm"]
+    u, P, X, seg = _hand_union(c, (1.0,))
+    with pytest.raises(TypeError, match="cam"):
+        _native.ose_seg_fwd(u["cam"].long(), u["pt"], u["vals"], seg[0], seg[3], P, X, HAND_WREG)
+    E = c["cam"].shape[0]
+    odd = torch.zeros(2 * E + 1, device=device)[1:].view(E, 2)
+    assert odd.is_contiguous() and odd.data_ptr() % 8 == 4
+    margin, eq, vo, hinge, w = HAND_ESFM
+    dP, dX = torch.full_like(c["P"], 7.0), torch.full_like(c["X"], 7.0)
+    one, tot = torch.ones(1, device=device), torch.ones(2, device=device)
+    with pytest.raises(RuntimeError, match="8-byte aligned"):
+        _native.esfm_bwd(c["cam_ptr"], c["pt_ptr"], c["perm"], c["cam"], c["pt"], odd, c["P"], c["X"], margin, w,
+                         hinge, eq, vo, one, tot, dP, dX)
+    assert float(dP.min()) == 7.0 and float(dX.min()) == 7.0  # nothing was launched
+
     data = gasfm_amd.SceneData.from_sparse(np.array([0, 1]), np.array([0, 0]), np.zeros((2, 2), np.float32), 2,
                                            1).to(device)
     lossf = ExpDepthRegularizedOSELoss(ose_conf(0.1))

@@ -6,8 +6,8 @@ GB/s from their algorithmic bytes, the whole HIP loss forward+ba
 reference formulation (code/loss_functions.py:85-123: dense Ps @ pts3D [m, 3, n], masks,
 gradient hook) run by torch on the same GPU for comparison.
 
---loss ose / depth: ExpDepthRegularizedOSELoss / DirectDepthLoss.  Each line is the median of
---trials timed blocks of --reps calls after a warm-up block, with the blocks' min and max; the
+Each line is the median of --trials timed blocks of --reps calls after a warm-up block, with the
+blocks' min and max.  --loss ose / depth: ExpDepthRegularizedOSELoss / DirectDepthLoss; the
 comparison is the same per-edge formula in torch ops (gather, elementwise, index_add backward).
 """
 import argparse
@@ -148,7 +148,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-dense", action="store_true")
     ap.add_argument("--loss", choices=("esfm", "ose", "depth"), default="esfm")
-    ap.add_argument("--trials", type=int, default=5, help="timed blocks per line (--loss ose / depth)")
+    ap.add_argument("--trials", type=int, default=5, help="timed blocks per line")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     sc = synthetic.config4()
@@ -170,14 +170,15 @@ def main():
                           "normalize_grad_wrt_valid_projections_only": True, "hinge_loss": True,
                           "hinge_loss_weight": 1.0}})
     lossf = ESFMLoss(conf)
-    res = []
 
-    def report(name, us, nbytes=None, **kw):
-        r = {"op": name, "us": round(us, 1), **kw}
+    def report(name, t, nbytes=None, **kw):
+        r = {"op": name, **t, **kw}
         if nbytes:
-            r["GBps"] = round(nbytes / us / 1e3, 1)
-        res.append(r)
+            r["GBps"] = round(nbytes / t["us"] / 1e3, 1)
         print(json.dumps(r), flush=True)
+
+    def timed(fn, reps):
+        return _time_spread(fn, reps, args.trials)
 
     (cam, pt), vals, cptr, pptr, perm = _edge_tensors(data)
     P = Ps.reshape(m, 12).contiguous()
@@ -185,17 +186,17 @@ def main():
     margin, w, hinge, eq, vo = lossf.kernel_conf()
     # algorithmic bytes: per edge cam + pt + 2 values (16 B) + each point's 4 coords once + cameras once
     fwd_bytes = 16 * E + 16 * n + 48 * m
-    report("esfm_fwd", _time(lambda: _native.esfm_fwd(cam, pt, vals, P, X, margin, w, hinge, part), args.reps),
+    report("esfm_fwd", timed(lambda: _native.esfm_fwd(cam, pt, vals, P, X, margin, w, hinge, part), args.reps),
            fwd_bytes)
     # compute_core_errors' reprojection error (gasfm_reproj_error): same bytes as esfm_fwd
-    report("reproj_error", _time(lambda: _native.reproj_error(cam, pt, vals, P, X), args.reps), fwd_bytes)
+    report("reproj_error", timed(lambda: _native.reproj_error(cam, pt, vals, P, X), args.reps), fwd_bytes)
     tot = _native.colsum(part)
     dloss = torch.ones(1, device=dev)
     dP, dX = torch.empty_like(P), torch.empty_like(X)
     # camera pass: pt + 2 values per edge + point coords; point pass: perm + cam + 2 values per edge + dX
     bwd_bytes = (12 * E + 16 * n + 48 * m) + (16 * E + 32 * n + 4 * n + 48 * m)
     report("esfm_bwd (cam + pt kernels)",
-           _time(lambda: _native.esfm_bwd(cptr, pptr, perm, cam, pt, vals, P, X, margin, w, hinge, eq, vo, dloss,
+           timed(lambda: _native.esfm_bwd(cptr, pptr, perm, cam, pt, vals, P, X, margin, w, hinge, eq, vo, dloss,
                                           tot, dP, dX), args.reps), bwd_bytes)
 
     Pr, Xr = Ps.clone().requires_grad_(True), X.clone().requires_grad_(True)
@@ -204,7 +205,7 @@ def main():
         Pr.grad = Xr.grad = None
         lossf({"Ps_norm": Pr, "pts3D": Xr}, data).backward()
 
-    report("ESFMLoss fwd+bwd (HIP, autograd)", _time(hip_step, args.reps), E=E)
+    report("ESFMLoss fwd+bwd (HIP, autograd)", timed(hip_step, args.reps), E=E)
     if not args.no_dense:
         nm = torch.zeros((m, n, 2), device=dev)
         nm[data.x.indices[0], data.x.indices[1]] = data.x.values
@@ -216,7 +217,7 @@ def main():
             Pr.grad = Xr.grad = None
             dense_reference_loss(Pr, Xr, norm_M, valid).backward()
 
-        report("reference formulation fwd+bwd (torch dense, same GPU)", _time(dense_step, max(3, args.reps // 4)),
+        report("reference formulation fwd+bwd (torch dense, same GPU)", timed(dense_step, max(3, args.reps // 4)),
                E=E)
 
 
