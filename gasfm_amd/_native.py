@@ -187,6 +187,13 @@ _SIGS = {
     "gasfm_fold_scene_rows_bwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
     "gasfm_adam_step": (_i32, [_vp, _vp, _i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                ctypes.c_double, _i64, _vp]),
+    "gasfm_grad_sumsq": (_i32, [_vp, _vp, _i32, _vp, _vp]),
+    "gasfm_grad_sumsq_finish": (_i32, [_vp, _i64, _vp, _vp, _vp]),
+    "gasfm_grad_clip": (_i32, [_vp, _vp, _i32, _i32, ctypes.c_double, _vp, _vp]),
+    "gasfm_adam_control": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_double, _vp, ctypes.c_double, ctypes.c_double, _i32,
+                                  ctypes.c_double, _vp]),
+    "gasfm_adam_step_ctl": (_i32, [_vp, _vp, _i32, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                   ctypes.c_double, _i32, ctypes.c_double, _vp]),
     "gasfm_union_fill_pad": (_i32, [_vp, _vp, _vp]),
     "gasfm_sos_union_tables": (_i32, [_vp, _vp]),
     "gasfm_point_tail_part_shape": (_i32, [_i64, _i32, _vp]),
@@ -1463,6 +1470,43 @@ def adam_step(tensors, chunks, n_chunks, lr, beta1, beta2, eps, weight_decay, st
     """gasfm_adam_step over device tables (uint8 tensors holding gasfm_adam_tensor / _chunk rows)."""
     check(lib().gasfm_adam_step(_p(tensors), _p(chunks), int(n_chunks), float(lr), float(beta1), float(beta2),
                                 float(eps), float(weight_decay), int(step), _stream(stream_of)), "gasfm_adam_step")
+
+
+CLIP_MODES = {None: 0, "norm": 1, "value": 2}  # GASFM_CLIP_*
+ADAM_CTL_FLOATS = 8  # sizeof(gasfm_adam_ctl) / 4: int32 skip, then grad_norm, gscale, step_size, inv_bc2_sqrt
+
+
+def grad_sumsq(tensors, chunks, n_chunks, partial, stream_of):
+    """partial[i] (fp64) = the sum of squares of chunk i's gradient values (gasfm_grad_sumsq)."""
+    check(lib().gasfm_grad_sumsq(_p(tensors), _p(chunks), int(n_chunks), _p(partial), _stream(stream_of)),
+          "gasfm_grad_sumsq")
+
+
+def grad_sumsq_finish(partial, n, total, norm):
+    """total (fp64) = the first n partials in a fixed order, norm (fp32) = sqrt(total)."""
+    check(lib().gasfm_grad_sumsq_finish(_p(partial), int(n), _p(total), _p(norm), _stream(total)),
+          "gasfm_grad_sumsq_finish")
+
+
+def grad_clip(tensors, chunks, n_chunks, mode, threshold, norm, stream_of):
+    """In-place clip of the table's gradients: mode 'norm' (coefficient from the device norm) or 'value'."""
+    check(lib().gasfm_grad_clip(_p(tensors), _p(chunks), int(n_chunks), CLIP_MODES[mode], float(threshold), _p(norm),
+                                _stream(stream_of)), "gasfm_grad_clip")
+
+
+def adam_control(ctl, sumsq, loss, lr, step, beta1, beta2, clip_mode, clip_th):
+    """gasfm_adam_control: this step's gasfm_adam_ctl from device values (lr: a float or a 0-d fp32 device tensor)."""
+    lr_dev = lr if torch.is_tensor(lr) else None
+    check(lib().gasfm_adam_control(_p(ctl), _p(sumsq), _p(loss), _p(lr_dev), 0.0 if lr_dev is not None else float(lr),
+                                   _p(step), float(beta1), float(beta2), CLIP_MODES[clip_mode], float(clip_th or 0.0),
+                                   _stream(ctl)), "gasfm_adam_control")
+
+
+def adam_step_ctl(tensors, chunks, n_chunks, ctl, beta1, beta2, eps, weight_decay, clip_mode, clip_th):
+    """gasfm_adam_step_ctl: the Adam update with its step constants, skip flag and clip coefficient from ctl."""
+    check(lib().gasfm_adam_step_ctl(_p(tensors), _p(chunks), int(n_chunks), _p(ctl), float(beta1), float(beta2),
+                                    float(eps), float(weight_decay), CLIP_MODES[clip_mode], float(clip_th or 0.0),
+                                    _stream(ctl)), "gasfm_adam_step_ctl")
 
 
 def union_fill_pad(pd, out, stream_of):

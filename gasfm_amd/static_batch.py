@@ -610,14 +610,21 @@ class StaticTrainer:
     optimizer: stepped after the gradients (train.py:97-100).  With ``capturable=True`` (torch's
     Adam / AdamW) its step is captured too, one graph per bucket over that bucket's gradient
     tensors, once its state exists (the first step of a run is eager); a Python-float learning rate
-    is then fixed at capture (pass a tensor lr to schedule it)."""
+    is then fixed at capture (pass a tensor lr to schedule it).  gasfm_amd.optim.Adam on its device
+    path (``capturable=True``) is captured the same way: its pointer tables for the bucket's gradients
+    are built first (``prepare()``), so the captured step is its kernel launches only.
 
-    def __init__(self, net, lossf, warmup=2, optimizer=None, max_buckets=32):
+    guard_loss: pass the bucket's static loss tensor to ``optimizer.step(loss=...)``, which then skips
+    the update on the device unless the loss is > 0 (train.py:133; gasfm_amd.optim.Adam's device path).
+    ``grad_norm``: the optimizer's device-side gradient norm of the last step, or None."""
+
+    def __init__(self, net, lossf, warmup=2, optimizer=None, max_buckets=32, guard_loss=False):
         """max_buckets: the least recently used bucket (its graphs and buffers) is dropped beyond it."""
         require_gasfm(net, "StaticTrainer")
         self.net, self.lossf = net, lossf
         self.max_buckets = max_buckets
         self.optimizer = optimizer
+        self.guard_loss = guard_loss
         self.opt_graphs = 0
         self.params = [p for p in net.parameters() if p.requires_grad]
         self.buckets = {}
@@ -660,20 +667,27 @@ class StaticTrainer:
         errs = [float(evaluation.reprojection_error_mean(d, p)) for p, d in zip(preds, datas)]
         return loss.detach(), errs
 
-    def _optimizer_step(self, b):
+    @property
+    def grad_norm(self):
+        return getattr(self.optimizer, "grad_norm", None)
+
+    def _optimizer_step(self, b, loss):
         opt = self.optimizer
+        kw = {"loss": loss} if self.guard_loss else {}
         if len(b) > 3:
             b[3].replay()
         elif b[1].captured and opt.defaults.get("capturable") and all(p in opt.state for p in self.params):
+            if hasattr(opt, "prepare"):
+                opt.prepare()  # tables for this bucket's gradient tensors: no copy inside the capture
             g = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
             with gc_paused(), torch.cuda.graph(g, pool=self.pool, capture_error_mode="thread_local"):
-                opt.step()
+                opt.step(**kw)
             g.replay()
             b.append(g)
             self.opt_graphs += 1
         else:
-            opt.step()
+            opt.step(**kw)
         self._refresh_if_bf16()
 
     def _refresh_if_bf16(self):
@@ -709,7 +723,7 @@ class StaticTrainer:
             self.fallbacks.append(why)
             loss, errs = self._eager(datas, inputs)
             if self.optimizer is not None:
-                self.optimizer.step()
+                self.optimizer.step(**({"loss": loss} if self.guard_loss else {}))
                 self._refresh_if_bf16()
             if not read_errors:
                 errs = torch.tensor([[e, 1.0] for e in errs], dtype=torch.float32)
@@ -739,7 +753,7 @@ class StaticTrainer:
         loss = b[1]()
         self._tick("replay" if b[1].captured else "eager")
         if self.optimizer is not None:
-            self._optimizer_step(b)
+            self._optimizer_step(b, loss)
             self._tick("optimizer")
         err = b[2]["err"][:st.B]
         if not read_errors:

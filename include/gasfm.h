@@ -925,6 +925,50 @@ typedef struct gasfm_adam_chunk {
 int gasfm_adam_step(const gasfm_adam_tensor* tensors, const gasfm_adam_chunk* chunks, int32_t n_chunks, double lr,
                     double beta1, double beta2, double eps, double weight_decay, int64_t step, void* stream);
 
+/* ---- gradient norm, clipping and a capturable Adam over the same tables (adam.hip) ----
+ * train.py:133-152 on the device: no atomics, no host reads, fixed summation orders (two runs are
+ * bitwise equal).  Rows of `tensors` need only g and numel for the two gradient entries.
+ *
+ * gasfm_grad_sumsq: partial[i] = sum of g^2 over chunk i, in fp64 (n_chunks doubles).
+ * gasfm_grad_sumsq_finish: total[0] = the n partials summed in a fixed order by one workgroup,
+ * norm[0] = sqrt(total) rounded to fp32; n = 0 gives 0.
+ * gasfm_grad_clip: in place, GASFM_CLIP_NORM g *= min(1, threshold / (*norm + 1e-6)) (torch's
+ * clip_grad_norm_: a NaN norm makes every value NaN, an inf norm 0 or NaN), GASFM_CLIP_VALUE
+ * g = clamp(g, -threshold, threshold) (norm unused; NaN stays NaN). */
+#define GASFM_CLIP_NONE 0
+#define GASFM_CLIP_NORM 1
+#define GASFM_CLIP_VALUE 2
+int gasfm_grad_sumsq(const gasfm_adam_tensor* tensors, const gasfm_adam_chunk* chunks, int32_t n_chunks,
+                     double* partial, void* stream);
+int gasfm_grad_sumsq_finish(const double* partial, int64_t n, double* total, float* norm, void* stream);
+int gasfm_grad_clip(const gasfm_adam_tensor* tensors, const gasfm_adam_chunk* chunks, int32_t n_chunks,
+                    int32_t mode, double threshold, const float* norm, void* stream);
+
+/* One optimizer step's constants, written on the device by gasfm_adam_control and read by
+ * gasfm_adam_step_ctl: nothing in either launch depends on a host value that changes per step. */
+typedef struct gasfm_adam_ctl {
+  int32_t skip;       /* 1: leave p, m, v and the step counter as they are */
+  float grad_norm;    /* sqrt(*sumsq), 0 without sumsq */
+  float gscale;       /* GASFM_CLIP_NORM: min(1, threshold / (grad_norm + 1e-6)); else 1 */
+  float step_size;    /* lr / (1 - beta1^t), evaluated in fp64 */
+  float inv_bc2_sqrt; /* 1 / sqrt(1 - beta2^t), evaluated in fp64 */
+  float reserved[3];
+} gasfm_adam_ctl;
+/* skip = loss != NULL && !(*loss > 0) (a NaN loss skips, as train.py's `if batch_loss.item() > 0`);
+ * t = *step + 1 and *step = t unless skipped (step: the fp32 device counter of torch's capturable
+ * Adam); lr = *lr_dev when lr_dev != NULL, else the host value.  sumsq: gasfm_grad_sumsq_finish's
+ * total, or NULL (required for GASFM_CLIP_NORM). */
+int gasfm_adam_control(gasfm_adam_ctl* ctl, const double* sumsq, const float* loss, const float* lr_dev,
+                       double lr, float* step, double beta1, double beta2, int32_t clip_mode,
+                       double clip_threshold, void* stream);
+/* gasfm_adam_step with step_size, inv_bc2_sqrt, skip and gscale from *ctl.  The gradient is clipped
+ * as it is read (g * gscale, or the clamp for GASFM_CLIP_VALUE), then weight decay, then the update:
+ * clip_grad_*() followed by optimizer.step(), with p.grad left as the backward wrote it.  A skipped
+ * step returns before any load or store of p, m, v. */
+int gasfm_adam_step_ctl(const gasfm_adam_tensor* tensors, const gasfm_adam_chunk* chunks, int32_t n_chunks,
+                        const gasfm_adam_ctl* ctl, double beta1, double beta2, double eps,
+                        double weight_decay, int32_t clip_mode, double clip_threshold, void* stream);
+
 /* ---- a union batch's per-scene global term folded into its cameras' rows (static_batch.hip) ----
  * model._fold_global (batch.py's union of scenes, one global node per scene): forward
  * out[c] = sv[c] + sg[soc[c]] ([m x width] rows, row strides given); backward dsg[s] = the sum over

@@ -70,6 +70,19 @@ def main():
                     help="also time the captured step with the next batch prepared on a second stream (prefetch)")
     ap.add_argument("--gasfm-adam", action="store_true",
                     help="--captured: gasfm_amd.optim.Adam (one HIP launch) instead of torch's captured fused Adam")
+    ap.add_argument("--capturable-adam", action="store_true",
+                    help="--captured: gasfm_amd.optim.Adam on its device path, its step captured per bucket; the "
+                         "per-scene errors are not read inside the timed step (read_errors=False)")
+    ap.add_argument("--grad-clip", choices=("norm", "value"), default=None,
+                    help="--capturable-adam / --reference-clip: loss.grad_clip_mode")
+    ap.add_argument("--grad-clip-th", type=float, default=1.0, help="loss.grad_clip_th")
+    ap.add_argument("--guard-loss", action="store_true",
+                    help="--capturable-adam: skip the update on the device unless the loss is > 0")
+    ap.add_argument("--reference-clip", action="store_true",
+                    help="--captured: train.py:133-152 after the captured forward + backward, as the reference "
+                         "runs it: .item() guard, cat-and-norm, torch's clip_grad_*, torch.optim.Adam.step()")
+    ap.add_argument("--step-stats", action="store_true",
+                    help="--captured: also report the median, min and max of the timed steps (fill + replay + optimizer)")
     ap.add_argument("--no-eager", action="store_true", help="skip the eager union mode (e.g. to profile --captured)")
     ap.add_argument("--progress", type=int, default=10, help="a progress line every this many batches")
     ap.add_argument("--phases", action="store_true",
@@ -214,12 +227,23 @@ def main():
         from gasfm_amd.static_batch import StaticTrainer
         # Adam (lr as above): torch's fused Adam with its step captured into each bucket's graph pair
         # (capturable=True), or --gasfm-adam: gasfm_amd.optim.Adam, one launch per step
-        if args.gasfm_adam:
+        new_modes = args.capturable_adam or args.reference_clip
+        params = [p for p in net.parameters() if p.requires_grad]
+        if args.capturable_adam:
+            from gasfm_amd.optim import Adam
+            copt = Adam(net.parameters(), lr=1e-4, capturable=True, grad_clip_mode=args.grad_clip,
+                        grad_clip_th=args.grad_clip_th if args.grad_clip else None,
+                        track_grad_norm=args.grad_clip is not None)
+        elif args.reference_clip:
+            copt = torch.optim.Adam(net.parameters(), lr=1e-4)  # train.py:97: the default (foreach) Adam
+        elif args.gasfm_adam:
             from gasfm_amd.optim import Adam
             copt = Adam(net.parameters(), lr=1e-4)
         else:
             copt = torch.optim.Adam(net.parameters(), lr=1e-4, fused=True, capturable=True)
-        trainer = StaticTrainer(net, lossf, optimizer=copt)
+        trainer = StaticTrainer(net, lossf, optimizer=None if args.reference_clip else copt,
+                                **({"guard_loss": True} if args.capturable_adam and args.guard_loss else {}))
+        per_step, pending = [], []
         t_prep = t_fb = t_opt = 0.0
         n_done = 0
         repro = []
@@ -245,17 +269,38 @@ def main():
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             copt.zero_grad()
-            loss, errs = trainer.step(datas, inputs)  # + Adam; reads the per-scene errors (a host sync)
-            repro.extend(errs)
+            if new_modes:
+                loss, err = trainer.step(datas, inputs, read_errors=False)
+                pending.append(err)
+                if args.reference_clip and loss.item() > 0:  # train.py:133-152
+                    torch.cat([p.grad.flatten() for p in params if p.grad is not None]).norm()
+                    if args.grad_clip == "norm":
+                        torch.nn.utils.clip_grad_norm_(params, args.grad_clip_th)
+                    elif args.grad_clip == "value":
+                        torch.nn.utils.clip_grad_value_(params, args.grad_clip_th)
+                    copt.step()
+            else:
+                loss, errs = trainer.step(datas, inputs)  # + Adam; reads the per-scene errors (a host sync)
+                repro.extend(errs)
             torch.cuda.synchronize()
             t2 = t3 = time.perf_counter()
+            for err in pending:  # outside the timed step
+                repro.extend(trainer.errors(err))
+            del pending[:]
             if it >= prime:
+                per_step.append(1e3 * (t2 - t1))
                 t_prep += t1 - t0
                 t_fb += t2 - t1
                 t_opt += t3 - t2
                 n_done += len(datas)
         tot = t_prep + t_fb + t_opt
-        return {"scenes_per_s": n_done / tot, "ms_per_step": 1e3 * tot / steps,
+        extra = {} if not new_modes else {
+            "optimizer": "capturable gasfm Adam" if args.capturable_adam else "reference sequence (torch)",
+            "grad_clip": args.grad_clip, "guard_loss": bool(args.guard_loss or args.reference_clip)}
+        if new_modes or args.step_stats:
+            extra.update({"ms_step_median": float(np.median(per_step)), "ms_step_min": min(per_step),
+                          "ms_step_max": max(per_step)})
+        return {**extra, "scenes_per_s": n_done / tot, "ms_per_step": 1e3 * tot / steps,
                 "ms_data_prep": 1e3 * t_prep / steps, "ms_fill_replay_errors_adam": 1e3 * t_fb / steps,
                 "prime_batches": prime, "s_prime": t_prime, "optimizer_graphs": trainer.opt_graphs,
                 "buckets": len(trainer.buckets), "captures_in_prime": caps_before,
