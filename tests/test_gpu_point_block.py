@@ -5,6 +5,7 @@ lin_scenepoint(relu(scenepoint_norm_layer(p))) :928-935; graph_conv_scenepoint2g
 the next block's norm_and_proj_scenepoint2proj + lin_r), evaluated in fp64 with autograd.
 Tolerance: outputs 2e-5 * max|ref| + 1e-5 elementwise; gradients normwise 1e-4 (fp32
 LayerNorm backward over 64 columns, weight gradients reduced over up to 70k rows).
+Tile remainders, workgroup edges, guarded / poisoned buffers and the entry points' contracts: test_gpu_point_edges.py.
 """
 import pytest
 import torch

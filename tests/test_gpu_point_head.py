@@ -6,6 +6,7 @@ Reference values: the same sequence in fp64.  Tolerance: the fused kernels sum i
 different order than aten, so each result must lie within 10x the fp32 aten result's own
 deviation from fp64 (plus 1e-6 of the output's scale) -- the principled bound used by the
 training-step tests.  Row 3 must be exactly 1; repeated runs must be bit-identical.
+Tile remainders, workgroup edges and guarded / poisoned buffers of the head: test_gpu_point_edges.py.
 """
 import pytest
 import torch
