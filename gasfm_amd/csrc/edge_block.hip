@@ -879,11 +879,11 @@ extern "C" int gasfm_edge_part_floats(int32_t which, int64_t E, int32_t n_items)
 extern "C" int gasfm_edge_prologue_fwd(const float* P, int64_t E, const float* ln_w, const float* ln_b,
                                        float eps, const float* W, const float* W2, const float* b,
                                        const float* b2, float* Y, int64_t ldY, const int32_t* pos, void* stream) {
+  if (E == 0) return GASFM_OK;  // nothing to do: the pointers of empty tensors are null
   GASFM_REQUIRE(E >= 0 && P && W && b && Y && (!W2) == (!b2), "gasfm_edge_prologue_fwd: bad args");
   GASFM_REQUIRE(!b2 || (aligned16(b2) && aligned16(W2)), "gasfm_edge_prologue_fwd: W2/b2 not 16-byte aligned");
   GASFM_REQUIRE(ldY >= NX && ldY % 4 == 0, "gasfm_edge_prologue_fwd: ldY < 64 or not a multiple of 4");
   GASFM_REQUIRE(aligned16(P) && aligned16(Y) && aligned16(b), "gasfm_edge_prologue_fwd: P/Y/b not 16-byte aligned");
-  if (E == 0) return GASFM_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (ln_w) {
     const int g = resident_grid(reinterpret_cast<const void*>(&edge_prologue_fwd_kernel<true>), kThreads, 0,
@@ -903,6 +903,7 @@ extern "C" int gasfm_edge_epilogue_fwd(const float* P, const float* P0, const in
                                        int64_t E, const float* ln_w, const float* ln_b, float eps, const float* Wp,
                                        int32_t ldWp, const float* bp, const float* Sp, const float* Sv,
                                        int64_t ldSv, const float* Sg, float scale, float* Pout, void* stream) {
+  if (E == 0) return GASFM_OK;  // nothing to do: the pointers of empty tensors are null
   GASFM_REQUIRE(E >= 0 && P && cam && pt && ln_w && ln_b && Wp && bp && Sp && Sv && Sg && Pout,
                 "gasfm_edge_epilogue_fwd: null pointer");
   GASFM_REQUIRE((P0 && ldWp == 34) || (!P0 && ldWp == 32), "gasfm_edge_epilogue_fwd: ldWp=%d vs P0", ldWp);
@@ -910,7 +911,6 @@ extern "C" int gasfm_edge_epilogue_fwd(const float* P, const float* P0, const in
   GASFM_REQUIRE(aligned16(P) && aligned16(Sp) && aligned16(Sv) && aligned16(Pout) &&
                     (!P0 || reinterpret_cast<uintptr_t>(P0) % 8 == 0),
                 "gasfm_edge_epilogue_fwd: P/Sp/Sv/Pout not 16-byte aligned (P0 8-byte)");
-  if (E == 0) return GASFM_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int g = resident_grid(reinterpret_cast<const void*>(&edge_epilogue_fwd_kernel), kThreads, 0, tiles_of(E),
                               kWaves);
@@ -923,11 +923,11 @@ extern "C" int gasfm_edge_epilogue_bwd(const gasfm_work_item* items, int32_t n_i
                                        const float* P, const float* P0, const float* ln_w, const float* ln_b,
                                        float eps, const float* Wp, int32_t ldWp, float scale, float* dSv,
                                        float* part_dsv, float* dP0, float* part_w, void* stream) {
+  if (n_items <= 0) return GASFM_OK;  // nothing to do: the pointers of empty tensors are null
   GASFM_REQUIRE(items && dPo && P && ln_w && ln_b && Wp && dSv && part_w, "gasfm_edge_epilogue_bwd: null pointer");
   GASFM_REQUIRE((P0 && dP0 && ldWp == 34) || (!P0 && ldWp == 32), "gasfm_edge_epilogue_bwd: ldWp=%d vs P0",
                 ldWp);
   GASFM_REQUIRE(aligned16(dPo) && aligned16(P), "gasfm_edge_epilogue_bwd: dPo/P not 16-byte aligned");
-  if (n_items <= 0) return GASFM_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int g = grid_ebwd(n_items);
   hipLaunchKernelGGL(edge_epilogue_bwd_kernel, dim3(g), dim3(kThreads), 0, st, items, n_items, dPo, P, P0, ln_w,
@@ -939,12 +939,12 @@ extern "C" int gasfm_edge_prologue_bwd(const float* dXL, int64_t ldX, const floa
                                        const float* ln_w, const float* ln_b, float eps, const float* W,
                                        const float* W2, const float* Wp, int32_t ldWp, float scale, float* dP,
                                        float* part, const float* dXLc, int64_t ldC, void* stream) {
-  GASFM_REQUIRE(dXL && P && W && dP && part && ldX >= (dXLc ? F : NX), "gasfm_edge_prologue_bwd: bad args");
+  if (E == 0) return GASFM_OK;  // nothing to do: the pointers of empty tensors are null
+  GASFM_REQUIRE(E > 0 && dXL && P && W && dP && part && ldX >= (dXLc ? F : NX), "gasfm_edge_prologue_bwd: bad args");
   GASFM_REQUIRE(!dXLc || (ldC >= F && ldC % 4 == 0 && aligned16(dXLc)), "gasfm_edge_prologue_bwd: dXLc rows");
   GASFM_REQUIRE(!dRes || Wp, "gasfm_edge_prologue_bwd: dRes needs Wp");
   GASFM_REQUIRE(aligned16(dXL) && ldX % 4 == 0 && aligned16(P) && (!dRes || aligned16(dRes)) && aligned16(dP),
                 "gasfm_edge_prologue_bwd: dXL/P/dRes/dP not 16-byte aligned");
-  if (E == 0) return GASFM_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int g = grid_pbwd(E);
   const bool ln = ln_w != nullptr, res = dRes != nullptr;
@@ -966,9 +966,9 @@ extern "C" int gasfm_edge_prologue_bwd(const float* dXL, int64_t ldX, const floa
 extern "C" int gasfm_segment_rowsum(const gasfm_work_item* items, int32_t n_items, const int32_t* perm,
                                     const float* X, int64_t ldX, float scale, float* out, float* part,
                                     void* stream) {
+  if (n_items <= 0) return GASFM_OK;  // nothing to do: the pointers of empty tensors are null
   GASFM_REQUIRE(items && X && out, "gasfm_segment_rowsum: null pointer");
   GASFM_REQUIRE(aligned16(X) && ldX % 4 == 0 && aligned16(out), "gasfm_segment_rowsum: alignment");
-  if (n_items <= 0) return GASFM_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int g = resident_grid(reinterpret_cast<const void*>(&segment_rowsum_kernel), kThreads, 0, n_items, kWaves);
   hipLaunchKernelGGL(segment_rowsum_kernel, dim3(g), dim3(kThreads), 0, st, items,

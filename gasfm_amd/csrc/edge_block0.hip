@@ -366,8 +366,8 @@ extern "C" int gasfm_edge0_part_rows(int32_t which, int64_t E, int32_t n_items) 
 extern "C" int gasfm_edge0_prologue_fwd(const float* P, int64_t E, const float* ln_w, const float* ln_b, float eps,
                                         const float* W0, const float* b0, float* XL, const int32_t* pos,
                                         void* stream) {
+  if (E == 0) return GASFM_OK;  // nothing to do: the pointers of empty tensors are null
   GASFM_REQUIRE(P && ln_w && ln_b && W0 && b0 && XL && aligned16(XL), "gasfm_edge0_prologue_fwd: bad args");
-  if (E == 0) return GASFM_OK;
   hipLaunchKernelGGL(edge0_prologue_fwd_kernel, dim3(grid_for(E, kT)), dim3(kT), 0,
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const float2*>(P), E, ln_w, ln_b, eps,
                      W0, b0, reinterpret_cast<float4*>(XL), pos);
@@ -377,9 +377,9 @@ extern "C" int gasfm_edge0_prologue_fwd(const float* P, int64_t E, const float* 
 extern "C" int gasfm_edge0_prologue_fwd_rows(const float* P, int64_t E, const float* ln_w, const float* ln_b,
                                              float eps, const float* W0, const float* b0, float* XL,
                                              const int32_t* perm, void* stream) {
+  if (E == 0) return GASFM_OK;  // nothing to do: the pointers of empty tensors are null
   GASFM_REQUIRE(P && ln_w && ln_b && W0 && b0 && XL && perm && aligned16(XL),
                 "gasfm_edge0_prologue_fwd_rows: bad args");
-  if (E == 0) return GASFM_OK;
   hipLaunchKernelGGL(edge0_prologue_fwd_rows_kernel, dim3(grid_for(E, kT)), dim3(kT), 0,
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const float2*>(P), E, ln_w, ln_b, eps,
                      W0, b0, reinterpret_cast<float4*>(XL), perm);
@@ -391,10 +391,10 @@ extern "C" int gasfm_edge0_epilogue_fwd(const float* P, const int32_t* cam, cons
                                         const float* ln_b_b, float eps, const float* Wp, const float* bp,
                                         const float* Wsk, const float* bsk, const float* Sp, const float* Sv,
                                         int64_t ldSv, const float* Sg, float scale, float* Pout, void* stream) {
+  if (E == 0) return GASFM_OK;  // nothing to do: the pointers of empty tensors are null
   GASFM_REQUIRE(P && cam && pt && Wp && bp && Wsk && bsk && Sp && Sv && Sg && Pout && aligned16(Sp) &&
                     aligned16(Sv) && aligned16(Pout) && ldSv >= 32 && ldSv % 4 == 0,
                 "gasfm_edge0_epilogue_fwd: bad args");
-  if (E == 0) return GASFM_OK;
   hipLaunchKernelGGL(edge0_epilogue_fwd_kernel, dim3(grid_for(E, kT / 8)), dim3(kT), 0,
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const float2*>(P), cam, pt, E, ln_a_w,
                      ln_a_b, ln_b_w, ln_b_b, eps, Wp, bp, Wsk, bsk, Sp, Sv, ldSv, Sg, scale, Pout);
@@ -406,9 +406,9 @@ extern "C" int gasfm_edge0_epilogue_bwd(const gasfm_work_item* items, int32_t n_
                                         const float* ln_b_w, const float* ln_b_b, float eps, const float* Wp,
                                         const float* Wsk, float scale, float* dSv, float* part_dsv, float* aux,
                                         float* part, void* stream) {
+  if (n_items <= 0) return GASFM_OK;  // nothing to do: the pointers of empty tensors are null
   GASFM_REQUIRE(items && dPo && P && Wp && Wsk && dSv && aux && part && aligned16(dPo) && aligned16(aux),
                 "gasfm_edge0_epilogue_bwd: bad args");
-  if (n_items <= 0) return GASFM_OK;
   hipLaunchKernelGGL(edge0_epilogue_bwd_kernel, dim3(grid_for(n_items, kT / kW)), dim3(kT), 0,
                      reinterpret_cast<hipStream_t>(stream), items, n_items, dPo, reinterpret_cast<const float2*>(P),
                      ln_a_w, ln_a_b, ln_b_w, ln_b_b, eps, Wp, Wsk, scale, dSv, part_dsv,
@@ -419,9 +419,9 @@ extern "C" int gasfm_edge0_epilogue_bwd(const gasfm_work_item* items, int32_t n_
 extern "C" int gasfm_edge0_prologue_bwd(const float* dXL, const float* P, const float* aux, int64_t E,
                                         const float* ln_w, const float* ln_b, float eps, const float* W0, float* dP,
                                         float* part, void* stream) {
+  if (E == 0) return GASFM_OK;  // nothing to do: the pointers of empty tensors are null
   GASFM_REQUIRE(dXL && P && ln_w && ln_b && W0 && dP && part && aligned16(dXL) && (!aux || aligned16(aux)),
                 "gasfm_edge0_prologue_bwd: bad args");
-  if (E == 0) return GASFM_OK;
   hipLaunchKernelGGL(edge0_prologue_bwd_kernel, dim3(grid_for(E, kT)), dim3(kT), 0,
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const float4*>(dXL),
                      reinterpret_cast<const float2*>(P), reinterpret_cast<const float4*>(aux), E, ln_w, ln_b, eps,

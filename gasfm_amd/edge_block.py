@@ -78,12 +78,15 @@ class EdgePrologueFn(torch.autograd.Function):
         if dtoken is not None and dtoken.stride(0) != 0:
             dRes = dtoken.contiguous()
         dP = torch.empty_like(P)
-        rows = _native.edge_part_floats(0, E) // (64 * 32 + 64 + 64)
-        part = torch.empty((rows, 64 * 32 + 64 + 64), dtype=torch.float32, device=P.device)
-        _native.edge_prologue_bwd(dXL, P, dRes, ln_w, ln_b, ctx.eps, W.contiguous(),
-                                  Wp.contiguous() if dRes is not None else None, PROJ_SCALE, dP, part,
-                                  W2.contiguous() if W2 is not None else None)
-        tot = _native.param_colsum(part.view(rows, -1), ctx.defer)
+        if E:
+            rows = _native.edge_part_floats(0, E) // (64 * 32 + 64 + 64)
+            part = torch.empty((rows, 64 * 32 + 64 + 64), dtype=torch.float32, device=P.device)
+            _native.edge_prologue_bwd(dXL, P, dRes, ln_w, ln_b, ctx.eps, W.contiguous(),
+                                      Wp.contiguous() if dRes is not None else None, PROJ_SCALE, dP, part,
+                                      W2.contiguous() if W2 is not None else None)
+            tot = _native.param_colsum(part.view(rows, -1), ctx.defer)
+        else:  # no edge, no launch: no partial row is written
+            tot = torch.zeros(64 * 32 + 64 + 64, dtype=torch.float32, device=P.device)
         dW = tot[:64 * 32].view(64, 32)
         db = tot[64 * 32:64 * 32 + 64]
         dgam = tot[64 * 32 + 64:64 * 32 + 96] if ctx.has_ln else None
@@ -345,6 +348,12 @@ def _epilogue_backward(ctx, saved, dPo, folded=None, dSg=None):
     pc = edges.plans["proj2view"]
     pp = edges.plans["proj2scenepoint"]
     dWp = None
+    if P.shape[0] == 0 and folded is None:  # no edge, no launch: every sum is empty
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        dSg = z(32) if dSg is None else dSg.zero_()
+        return (None, z(0, 2) if P0 is not None else None, dPo, z(edges.n, 32), z(edges.m, 32),
+                dSg.view(ctx.sg_shape), None if ctx.wp_by_cam else torch.zeros_like(Wp), z(32), None, None, None,
+                None, None)
     if folded is not None:  # part_dsv None: merged together with the camera plan's dXR (edge_cam_pbwd)
         dSv, part_dsv, dP0 = folded
     else:
@@ -526,10 +535,13 @@ class Block0PrologueFn(torch.autograd.Function):
         dXL = torch.zeros((E, 8), dtype=torch.float32, device=P.device) if dXL is None else dXL.contiguous()
         aux = daux.contiguous() if daux is not None and daux.stride(0) != 0 else None
         dP = torch.empty_like(P)
-        rows = _native.edge0_part_rows(0, E)
-        part = torch.empty((rows, 28), dtype=torch.float32, device=P.device)
-        _native.edge0_prologue_bwd(dXL, P, aux, ln_w, ln_b, ctx.eps, W0.contiguous(), dP, part)
-        tot = _native.colsum(part)
+        if E:
+            rows = _native.edge0_part_rows(0, E)
+            part = torch.empty((rows, 28), dtype=torch.float32, device=P.device)
+            _native.edge0_prologue_bwd(dXL, P, aux, ln_w, ln_b, ctx.eps, W0.contiguous(), dP, part)
+            tot = _native.colsum(part)
+        else:  # no edge, no launch: no partial row is written
+            tot = torch.zeros(28, dtype=torch.float32, device=P.device)
         return dP, tot[24:26], tot[26:28], tot[:16].view(8, 2), tot[16:24], None, None, None
 
 
@@ -562,6 +574,10 @@ def _epilogue0_backward(ctx, saved, dPo, bnd=None):
     dev = P.device
     E = P.shape[0]
     pc, pp = edges.plans["proj2view"], edges.plans["proj2scenepoint"]
+    if E == 0 and bnd is None:  # no edge, no launch: every sum is empty
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        return (None, z(0, 4), z(edges.n, 32), z(edges.m, 32), z(32).view(ctx.sg_shape), torch.zeros_like(Wp), z(32),
+                None, None, z(2), z(2), torch.zeros_like(Wsk), z(Wsk.shape[0]), None, None)
     dSv = bnd[0] if bnd is not None else torch.empty((edges.m, 32), dtype=torch.float32, device=dev)
     part_dsv = torch.empty((max(pc.n_part_rows, 1), 32), dtype=torch.float32, device=dev)
     aux = torch.empty((E, 4), dtype=torch.float32, device=dev)
