@@ -21,6 +21,7 @@ view_block.hip, global_vec.hip); only the camera side's two m x 1024 x 1024 GEMM
 go through hipBLASLt (or the HIP MFMA GEMMs, view_block._mm).
 """
 import os
+from collections import namedtuple
 
 import torch
 
@@ -480,25 +481,45 @@ def _boundary_buffers(m, n_xr, dev):
     return flat[:m * 32].view(m, 32), flat[m * 32:m * 32 + 32], flat[m * 32 + 32:].view(n_xr, 32)
 
 
-class _EpiState:
-    def __init__(self, eps, edges, sg_shape, defer, wp_by_cam=False, defer_b=False):
-        self.eps, self.edges, self.sg_shape, self.defer = eps, edges, sg_shape, defer
-        self.wp_by_cam = wp_by_cam
-        self.defer_b = defer_b
+_EpiState = namedtuple("_EpiState", "eps edges sg_shape defer wp_by_cam defer_b", defaults=(False, False))
+
+
+# The arguments of EdgeEpilogueFn.forward and Block0EpilogueFn.forward after ctx, and of EdgeCamFn.forward
+# after ctx and P, by name (SeamFn / Seam0Fn: an epilogue record's, then a CamArgs'); held to the signatures
+# by tests/test_block_plumbing_cpu.py.
+EpilogueArgs = namedtuple("EpilogueArgs", "P P0 token Sp Sv Sg Wp bp ln_w ln_b eps edges wp_by_cam", defaults=(False,))
+Epilogue0Args = namedtuple("Epilogue0Args", "P token Sp Sv Sg Wp bp lna_w lna_b lnb_w lnb_b Wsk bsk eps edges")
+CamArgs = namedtuple("CamArgs", "ln_w ln_b Wpt bpt Wc bc Wp eps pos XR att bias plan heads slope plan_partial shard "
+                     "P0 dwp", defaults=(None, None, None, False))
 
 
 class PendingEpilogue:
-    """Block b's EdgeEpilogueFn.apply arguments (block0: Block0EpilogueFn's), held so that block b+1
-    can run it together with its own prologue (SeamFn / Seam0Fn); materialize() runs it alone (any
-    other consumer of P')."""
+    """Block b's EdgeEpilogueFn.apply arguments (an EpilogueArgs; block 0: Block0EpilogueFn's, an
+    Epilogue0Args), held so that block b+1 can run it together with its own prologue (seam: SeamFn /
+    Seam0Fn); materialize() runs it alone (any other consumer of P')."""
 
-    def __init__(self, args, block0=False):
-        self.args = args
-        self.block0 = block0
-        self._P = None
+    def __init__(self, args):
+        self.args, self.block0, self._P = args, isinstance(args, Epilogue0Args), None
 
-    def seam_fn(self):
-        return Seam0Fn if self.block0 else SeamFn
+    def seam_ok(self):
+        """The epilogue's shapes are the seam kernel's: P [E, 32] with P0 [E, 2] or none, lin_proj
+        [32, 32 (+2)] and a LayerNorm (block 0: P [E, 2], lin_proj and the skip projection [32, 2]),
+        the one-row (or folded) global term."""
+        a = self.args
+        if self.block0:
+            ok = a.P.shape[1] == 2 and tuple(a.Wp.shape) == (32, 2) and tuple(a.Wsk.shape) == (32, 2)
+        else:
+            ok = (a.P.shape[1] == 32 and a.ln_w is not None
+                  and tuple(a.Wp.shape) == ((32, 34) if a.P0 is not None else (32, 32)))
+        return (a.P.is_cuda and a.P.dtype == torch.float32 and a.P.dim() == 2 and ok and a.Sg.numel() == 32
+                and a.Sp.shape[1] == 32 and a.Sv.shape[1] == 32)
+
+    def seam(self, cam):
+        """This epilogue and the next block's EdgeCamFn (cam: its CamArgs) in one kernel:
+        (P', XLp, camera aggregates, token); P' is kept for materialize()."""
+        out = (Seam0Fn if self.block0 else SeamFn).apply(*self.args, *cam)
+        self._P = out[0]
+        return out
 
     def materialize(self):
         if self._P is None:

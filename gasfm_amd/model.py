@@ -28,8 +28,8 @@ from torch.nn import Identity, LayerNorm, Linear, Module, ModuleList, ReLU, Sequ
 
 from . import _native, dense, edge_block, edge_ops, point_block, view_block
 from .attention import AttnPlan, GatAttentionFn, gat_attention
-from .edge_block import (Block0EpilogueFn, Block0PrologueFn, DualAttentionFn, EdgeCamFn, EdgeEpilogueFn,
-                         EdgePrologueFn, PendingEpilogue, SeamFn, materialize)
+from .edge_block import (Block0PrologueFn, CamArgs, DualAttentionFn, EdgeCamFn, EdgePrologueFn, Epilogue0Args,
+                         EpilogueArgs, PendingEpilogue, materialize)
 from .gatv2 import GATv2Conv, zero_target_rows
 
 
@@ -65,19 +65,56 @@ def _cam_sharded(shard):
     return shard is not None and shard.cams is not None
 
 
-def _wrap_boundary(shard, sv, sg, carry):
-    """sv / sg (replicated, read by the local edges) get their gradients summed over ranks by ONE
-    all-reduce -- together with the next block's camera target rows XRc when the view hub left
-    them in carry (their gradient, from the next block's camera attention on the local edges, is
-    partial too), so that block skips its own all-reduce."""
-    if shard is None:
-        return sv, sg
-    if carry is not None and "XRc" in carry and not carry.get("XRc_wrapped", False):
-        sv, sg, xrc = replicated_to_local_n(shard, sv, sg, carry["XRc"])
-        carry["XRc"] = xrc
-        carry["XRc_wrapped"] = True
-        return sv, sg
-    return replicated_to_local_n(shard, sv, sg)
+class BlockCarry:
+    """What the fused hubs of one forward hand on, one field per hand-off; None: not set.  (The
+    carry itself is None on the CPU and for stateless features: no hubs run.)
+
+    field      producer (in block b)               consumer
+    XRp        point hub                           block b+1's point attention (its target rows)
+    pts_skip   point hub                           block b+1's point tail (its state skip)
+    SA         point hub                           block b's edge epilogue (point term)
+    XLs2g      point hub                           block b's points->global conv (its lin_l rows)
+    XRc        view hub, or the block exchange     block b+1's camera attention (its target rows), via
+                                                   block b's _edge_terms (the shard boundary's wrap)
+    view_skip  view hub                            block b+1's view tail (its state skip)
+    SV         view hub, or the block exchange     block b's edge epilogue (camera term)
+    XLv2g      view hub                            block b's views->global conv (its lin_l rows)
+    exch       view hub (camera-sharded)           block b's global convs: the BlockExchange
+    rows_own   view hub (camera-sharded)           block b's global convs: this rank's (SV, XR) rows
+    SG         global chain (or global hub)        block b's edge epilogue (global term)
+    pre_glob   global chain (or global hub)        block b+1's global convs: (XRv, XRp, state skip)
+    """
+    __slots__ = ("XRp", "pts_skip", "SA", "XLs2g", "XRc", "view_skip", "SV", "XLv2g", "exch", "rows_own", "SG",
+                 "pre_glob")
+
+    def __init__(self):
+        for name in self.__slots__:
+            setattr(self, name, None)
+
+    def take(self, name):
+        """The field's value; the field is cleared."""
+        value = getattr(self, name)
+        setattr(self, name, None)
+        return value
+
+    def pending(self):
+        """Names of the fields still set (none after a whole forward)."""
+        return [name for name in self.__slots__ if getattr(self, name) is not None]
+
+
+def _edge_terms(pfu, pts, view, glob, plans, carry):
+    """A block's epilogue terms (sp, sv, sg): the hubs' where they ran (carry), folded over the scenes
+    of a SceneBatch.  sv / sg (replicated, read by the local edges) get their gradients summed over
+    ranks by ONE all-reduce -- together with the next block's camera target rows XRc when the view
+    hub left them in carry (their gradient, from that block's camera attention on the local edges,
+    is partial too): an XRc taken from the carry is wrapped, and that block runs no all-reduce."""
+    hub = (carry.take("SA"), carry.take("SV"), carry.take("SG")) if carry is not None else ()
+    sp, sv, sg = pfu.node_terms(pts, view, glob, *hub)
+    if carry is None or carry.XRc is None:
+        sv, sg = replicated_to_local_n(plans.get("_shard"), sv, sg)
+    else:
+        sv, sg, carry.XRc = replicated_to_local_n(plans.get("_shard"), sv, sg, carry.XRc)
+    return (sp, *_fold_global(sv, sg, plans))
 
 
 class _LazySharded:
@@ -232,53 +269,54 @@ class ViewAndScenePoint2Global(Module):
             self.norm_pre_mlp = LayerNorm(n_feat_global_out)
         self.mlp = get_linear_layers((2 + n_hidden_layers_global_update) * [n_feat_global_out], norm=False)
 
-    def forward_plan(self, view, pts, plan_v2g, plan_s2g, prev, plan_s2g_partial=None, shard=None, xl_pts=None,
-                     xl_view=None, pre_glob=None, plan_v2g_partial=None, chain=None, exch=None, rows=None):
-        """xl_pts / xl_view: the convs' lin_l(pts) / lin_l(view) when already computed (hubs);
-        pre_glob: (XR_view2global, XR_scenepoint2global, skip of prev) from GlobalHubFn.
+    def forward_plan(self, view, pts, plan_v2g, plan_s2g, prev, plan_s2g_partial=None, shard=None,
+                     plan_v2g_partial=None, chain=None, carry=None):
+        """Returns (g, rows).  carry (BlockCarry): its pre_glob, XLv2g, XLs2g (the convs' lin_l(view) /
+        lin_l(pts)) and exch are taken where the hubs set them.
         Camera-sharded (shard.cams): view holds this rank's camera rows and both attentions
-        exchange partial states in one all-gather (distributed.ShardedGlobalAttentionFn).
+        exchange partial states in one all-gather (distributed.ShardedGlobalAttentionFn); with exch
+        the view hub's rows_own leave in it too (ShardedGlobalExchangeFn) and rows is the gathered
+        [m, 32] (SV, XRc), else None.
         chain: dense.chain_params of this update and the consumers of its output; the tail then runs
-        as one GlobalChainFn and forward_plan returns its (g, SG[, XRv, XRp]) tuple.
-        exch / rows: the camera-sharded block exchange (distributed.BlockExchange) and the view hub's
-        own (SV, XR) rows: both convs' partial rows and those rows leave in ONE all-gather
-        (ShardedGlobalExchangeFn); rows["SV"], rows["XRc"] are set to the gathered [m, 32] rows."""
+        as one GlobalChainFn and g is its (g, SG[, XRv, XRp]) tuple."""
         assert self.stateful == (prev is not None)
         cv, c = self.graph_conv_view2global, self.graph_conv_scenepoint2global
+        pre_glob = XLv = XLp = exch = None
+        if carry is not None:
+            pre_glob, XLv, XLp, exch = (carry.take(k) for k in ("pre_glob", "XLv2g", "XLs2g", "exch"))
         if pre_glob is not None:
             XRv, XRp, prev = pre_glob
         else:
             xv = dense.sequential(self.norm_and_proj_global2view, prev) if prev is not None else None
             xp = dense.sequential(self.norm_and_proj_global2scenepoint, prev) if prev is not None else None
             XRv, XRp = _target_row(cv, xv, view, plan_v2g.num_targets), _target_row(c, xp, pts, plan_s2g.num_targets)
-        XLv = xl_view if xl_view is not None else dense.linear(view, cv.lin_l)
-        XLp = xl_pts if xl_pts is not None else dense.linear(pts, c.lin_l)
-        if _cam_sharded(shard) and exch is not None:
+        XLv = XLv if XLv is not None else dense.linear(view, cv.lin_l)
+        XLp = XLp if XLp is not None else dense.linear(pts, c.lin_l)
+        rows = None
+        if exch is not None:  # camera-sharded, from the view hub
             from .distributed import ShardedGlobalExchangeFn
-            x, SVf, XRf = ShardedGlobalExchangeFn.apply(
-                XLv, XRv, cv.att, cv._bias(XLv), XLp, XRp, c.att, c.bias, rows["own"][0], rows["own"][1],
+            x, *rows = ShardedGlobalExchangeFn.apply(
+                XLv, XRv, cv.att, cv._bias(XLv), XLp, XRp, c.att, c.bias, *carry.take("rows_own"),
                 (plan_v2g, plan_s2g), c.heads, c.negative_slope, shard, exch, pre_glob is not None)
-            rows.update(SV=SVf, XRc=XRf)
-            return self._global_tail(x, prev, chain)
-        if _cam_sharded(shard):
+        elif _cam_sharded(shard):
             from .distributed import ShardedGlobalAttentionFn
             x = ShardedGlobalAttentionFn.apply(
                 XLv, XRv, cv.att, cv._bias(XLv), XLp, XRp, c.att, c.bias,
                 (plan_v2g, plan_v2g_partial, plan_s2g, plan_s2g_partial), c.heads, c.negative_slope, shard)
-            return self._global_tail(x, prev, chain)
-        if shard is None and XLv.is_cuda and plan_v2g.num_targets == 1 and plan_s2g.num_targets == 1 \
+        elif shard is None and XLv.is_cuda and plan_v2g.num_targets == 1 and plan_s2g.num_targets == 1 \
                 and cv.heads == c.heads and cv.negative_slope == c.negative_slope:
             from .attention import GlobalPairFn
             x = GlobalPairFn.apply(XLv, XRv, cv.att, cv._bias(XLv), XLp, XRp, c.att, c._bias(XLp), plan_v2g, plan_s2g,
                                    c.heads, c.negative_slope)
-            return self._global_tail(x, prev, chain)
-        v2g = gat_attention(XLv, XRv, cv.att, cv._bias(XLv), plan_v2g, cv.heads, cv.negative_slope)
-        if shard is None:
-            s2g = gat_attention(XLp, XRp, c.att, c._bias(XLp), plan_s2g, c.heads, c.negative_slope)
-        else:  # points are sharded, the global target is replicated
-            s2g = ShardedAttentionFn.apply(XLp, replicated_to_local(XRp, shard), c.att, c.bias, plan_s2g,
-                                           plan_s2g_partial, c.heads, c.negative_slope, shard)
-        return self._global_tail(torch.cat([v2g, s2g], dim=1), prev, chain)
+        else:
+            v2g = gat_attention(XLv, XRv, cv.att, cv._bias(XLv), plan_v2g, cv.heads, cv.negative_slope)
+            if shard is None:
+                s2g = gat_attention(XLp, XRp, c.att, c._bias(XLp), plan_s2g, c.heads, c.negative_slope)
+            else:  # points are sharded, the global target is replicated
+                s2g = ShardedAttentionFn.apply(XLp, replicated_to_local(XRp, shard), c.att, c.bias, plan_s2g,
+                                               plan_s2g_partial, c.heads, c.negative_slope, shard)
+            x = torch.cat([v2g, s2g], dim=1)
+        return self._global_tail(x, prev, chain), rows
 
     def _global_tail(self, x, prev, chain=None):
         if chain is not None:
@@ -303,24 +341,6 @@ def _target_row(conv, x_tgt, ref, n=1):
     if x_tgt is None:
         return zero_target_rows(conv.lin_r, n, ref)
     return dense.linear(x_tgt, conv.lin_r)
-
-
-def _seam_ok(args):
-    """The epilogue's shapes are the seam kernel's: P [E, 32] with P0 [E, 2] or none, lin_proj
-    [32, 32 (+2)], a LayerNorm, the one-row (or folded) global term."""
-    P, P0, _, sp, sv, sg, W, b, ln_w, ln_b = args[:10]
-    return (P.is_cuda and P.dtype == torch.float32 and P.dim() == 2 and P.shape[1] == 32 and ln_w is not None
-            and tuple(W.shape) == ((32, 34) if P0 is not None else (32, 32)) and sg.numel() == 32
-            and sp.shape[1] == 32 and sv.shape[1] == 32)
-
-
-def _seam0_ok(args):
-    """Block 0's epilogue shapes are the block-0 seam kernel's: P [E, 2], lin_proj and the skip
-    projection [32, 2], the one-row (or folded) global term."""
-    P, _, sp, sv, sg, W, _, _, _, _, _, Wsk = args[:12]
-    return (P.is_cuda and P.dtype == torch.float32 and P.dim() == 2 and P.shape[1] == 2
-            and tuple(W.shape) == (32, 2) and tuple(Wsk.shape) == (32, 2) and sg.numel() == 32
-            and sp.shape[1] == 32 and sv.shape[1] == 32)
 
 
 class FoldGlobalFn(torch.autograd.Function):
@@ -465,35 +485,35 @@ class GraphAttnSfMGlobalFeatureUpdate(Module):
         a, b = self.proj2scenepoint.graph_conv.lin_l, self.proj2view.graph_conv.lin_l
         return torch.cat([a.weight, b.weight], 0), torch.cat([a.bias, b.bias], 0)
 
-    def forward_fused(self, XL, plans, prev_pt=None, prev_view=None, prev_glob=None, xl_sorted=False, carry=None,
-                      pfu=None, nxt=None, attend=None):
-        """Node side of the update given XL = [lin_l_point(P_hat) | lin_l_camera(P_hat)] [E, 64]
-        (point half in point-segment order when xl_sorted), or attend(XRp, XRc) -> (point
-        aggregates, camera aggregates) (the fused prologue + camera attention, edge_cam_attend).
+    def prologue(self, P, plans, ln=None, Wp=None):
+        """(XL, token) of EdgePrologueFn on P, where the fused prologue + camera attention does not
+        apply.  ln / Wp: the block's LayerNorm and lin_proj weight; none for the final update."""
+        (W, b), (W2, b2) = self.lin_l_pair()
+        ln_w, ln_b, eps = (ln.weight, ln.bias, ln.eps) if ln is not None else (None, None, 1e-5)
+        return EdgePrologueFn.apply(P, ln_w, ln_b, W, b, Wp, eps, plans["proj2scenepoint"].pos, W2, b2)
 
-        carry: per-forward dict through which PointHubFn / ViewHubFn hand the next block its
-        target rows ("XRp", "XRc") and state skips ("pts_skip", "view_skip"), and this block its
-        "SA" / "SV" / "XLs2g" / "XLv2g" terms; pfu / nxt: this block's projection-feature update
-        and the next block's (or the final) GraphAttnSfMGlobalFeatureUpdate, whose Proj2ScenePoint
-        and Proj2View are the hubs' next-block consumers (None: no next consumer)."""
+    def forward_fused(self, XL, plans, prev_pt=None, prev_view=None, prev_glob=None, carry=None, pfu=None, nxt=None,
+                      attend=None):
+        """Node side of the update given XL = [lin_l_point(P_hat) | lin_l_camera(P_hat)] [E, 64]
+        (point half in point-segment order when the point plan has pos), or attend(XRp, XRc) ->
+        (point aggregates, camera aggregates) (the fused prologue + camera attention, EdgeCamAttend).
+        carry: the forward's BlockCarry (its docstring lists what travels); pfu / nxt: this block's
+        projection-feature update and the next block's (or the final) GraphAttnSfMGlobalFeatureUpdate,
+        whose Proj2ScenePoint and Proj2View are the hubs' next-block consumers (None: no next consumer)."""
         sp, sv = self.proj2scenepoint, self.proj2view
         pp, pc = plans["proj2scenepoint"], plans["proj2view"]
         shard = plans.get("_shard")
-        if carry is not None and "XRp" in carry:
-            XRp, prev_pt = carry.pop("XRp"), carry.pop("pts_skip")
+        if carry is not None and carry.XRp is not None:
+            XRp, prev_pt = carry.take("XRp"), carry.take("pts_skip")
         else:
             XRp = sp.target_rows(prev_pt, pp.num_targets)
         cams = _cam_sharded(shard)
-        if carry is not None and "XRc" in carry:
-            XRc, prev_view = carry.pop("XRc"), carry.pop("view_skip")
-            wrapped = carry.pop("XRc_wrapped", False)
+        if carry is not None and carry.XRc is not None:  # wrapped for the shard boundary by _edge_terms
+            XRc, prev_view = carry.take("XRc"), carry.take("view_skip")
         else:
             if cams and prev_view is not None:
                 raise RuntimeError("camera-sharded execution needs the fused view hubs (stateful block without carry)")
-            XRc = sv.target_rows(prev_view, pc.num_targets)
-            wrapped = False
-        if not wrapped:
-            XRc = replicated_to_local(XRc, shard)
+            XRc = replicated_to_local(sv.target_rows(prev_view, pc.num_targets), shard)
         cp, cc = sp.graph_conv, sv.graph_conv
         hubs = carry is not None and self.output_global and nxt is not None
         vsg = self.view_and_scenepoint2global if hubs else None
@@ -503,7 +523,7 @@ class GraphAttnSfMGlobalFeatureUpdate(Module):
         else:
             agg_p, agg_c = DualAttentionFn.apply(XL, XRp, XRc, cp.att, cc.att, cp.bias, cc.bias, pp, pc, cp.heads,
                                                  cp.negative_slope, plans.get("_partial", {}).get("proj2view"), shard,
-                                                 xl_sorted)
+                                                 pp.pos is not None)
         exch = None
         if cams:  # this rank's camera rows only from here on (distributed.py, camera sharding)
             from .distributed import BlockExchange, own_rows
@@ -518,31 +538,27 @@ class GraphAttnSfMGlobalFeatureUpdate(Module):
                 skip, SV, XLv, XRn = view_block.hub(view, hv, getattr(self, "_proj_bf16", False), packed=cams,
                                                     out=exch.rows_out() if exch is not None else None)
                 if exch is not None:  # SV and XR of every rank travel with the global convs' partial rows
-                    carry.update(exch=exch, rows_own=(SV, XRn))
-                elif cams:  # every rank's edges read all cameras' SV and XR: one all-gather
-                    from .distributed import gather_rows
-                    SV, XRn = gather_rows(shard, SV, XRn)
-                if exch is None:
-                    carry.update(XRc=XRn, SV=SV)
-                carry.update(view_skip=skip, XLv2g=XLv)
+                    carry.exch, carry.rows_own = exch, (SV, XRn)
+                else:
+                    if cams:  # every rank's edges read all cameras' SV and XR: one all-gather
+                        from .distributed import gather_rows
+                        SV, XRn = gather_rows(shard, SV, XRn)
+                    carry.XRc, carry.SV = XRn, SV
+                carry.view_skip, carry.XLv2g = skip, XLv
             elif cams:
                 raise RuntimeError("camera-sharded execution needs the fused view hub shapes")
         if hp is not None and point_block.FUSED_TAIL_HUB and point_block.tail_fusable(sp, agg_p, prev_pt):
             # the point tail and hub as one forward launch (round 6, PointTailHubFn)
-            pts, skip, SA, XLs, XRn = point_block.tail_hub(sp, agg_p, prev_pt, hp)
-            carry.update(XRp=XRn, pts_skip=skip, SA=SA, XLs2g=XLs)
+            pts, carry.pts_skip, carry.SA, carry.XLs2g, carry.XRp = point_block.tail_hub(sp, agg_p, prev_pt, hp)
         else:
             pts = sp.tail(agg_p, prev_pt)
             if hp is not None and point_block._rows_ok(pts, point_block.P_W):
-                skip, SA, XLs, XRn = point_block.hub(pts, hp)
-                carry.update(XRp=XRn, pts_skip=skip, SA=SA, XLs2g=XLs)
+                carry.pts_skip, carry.SA, carry.XLs2g, carry.XRp = point_block.hub(pts, hp)
         return self._finish(pts, view, plans, prev_glob, carry, pfu, nxt)
 
     def _exchange_ok(self, vsg):
         """The merged block exchange applies: both global convs on the fused kernels' shapes (H = 4,
         C in {256, 16}, global_attn.hip) and the fused view hub's 32-wide SV / XR."""
-        if vsg is None:
-            return False
         cvg, csg = vsg.graph_conv_view2global, vsg.graph_conv_scenepoint2global
         return (cvg.heads == 4 and csg.heads == 4 and cvg.att.numel() in (64, 1024) and csg.att.numel() in (64, 1024)
                 and cvg.negative_slope == csg.negative_slope and cvg.bias is not None and csg.bias is not None)
@@ -554,35 +570,6 @@ class GraphAttnSfMGlobalFeatureUpdate(Module):
         return (EDGE_CAM and cc.heads == 4 and cc.out_channels == 8 and cp.heads == 4 and cp.out_channels == 8
                 and plans["proj2view"].perm is None)
 
-    def edge_cam_attend(self, P, ln_w, ln_b, eps, Wp, plans, holder, P0=None, dwp=False):
-        """attend callback of forward_fused: EdgeCamFn on P (lin_l of both convs, the camera
-        attention; XLp written in point order) then the point attention on XLp.  The prologue's
-        token (see EdgePrologueFn) is left in holder["token"].  dwp: the camera Function returns
-        the block's lin_proj gradient (EdgeCamFn's dwp; P0 its skip input)."""
-        (W, b), (W2, b2) = self.lin_l_pair()
-        pp, pc = plans["proj2scenepoint"], plans["proj2view"]
-        cp, cc = self.proj2scenepoint.graph_conv, self.proj2view.graph_conv
-        pos = pp.pos
-
-        def attend(XRp, XRc):
-            cam_args = (ln_w, ln_b, W, b, W2, b2, Wp, eps, pos, XRc, cc.att, cc.bias, pc, cc.heads, cc.negative_slope,
-                        plans.get("_partial", {}).get("proj2view"), plans.get("_shard"), P0, dwp)
-            Pe = P
-            if isinstance(Pe, PendingEpilogue) and Pe.block0 and ln_w is None:
-                Pe = Pe.materialize()  # the block-0 seam is built for a LayerNorm prologue only
-            if isinstance(Pe, PendingEpilogue):  # the previous block's epilogue in the same kernel
-                Pn, XLp, agg_c, token = Pe.seam_fn().apply(*Pe.args, *cam_args)
-                Pe._P = Pn
-                holder["P"] = Pn
-            else:
-                XLp, agg_c, token = EdgeCamFn.apply(Pe, *cam_args)
-                holder["P"] = Pe
-            holder["token"] = token
-            agg_p = GatAttentionFn.apply(XLp, XRp, cp.att, cp.bias, pp, cp.heads, cp.negative_slope,
-                                         pos is not None)[0]
-            return agg_p, agg_c
-        return attend
-
     def forward_plan(self, P_hat, plans, prev_pt=None, prev_view=None, prev_glob=None):
         shard = plans.get("_shard")
         pts = self.proj2scenepoint.forward_plan(P_hat, plans["proj2scenepoint"], prev_pt)
@@ -593,39 +580,56 @@ class GraphAttnSfMGlobalFeatureUpdate(Module):
     def _finish(self, pts, view, plans, prev_glob, carry=None, pfu=None, nxt=None):
         glob = None
         if self.output_global or self.global2view_and_global2scenepoint_enabled:
-            pre_glob = carry.pop("pre_glob", None) if carry is not None else None
             chain = None
+            nv = nxt.view_and_scenepoint2global if nxt is not None and nxt.output_global else None
             if GLOBAL_CHAIN and carry is not None and pfu is not None and self.output_global:
-                nv = nxt.view_and_scenepoint2global if nxt is not None and getattr(nxt, "output_global", False) \
-                    else None
                 chain = dense.chain_params(self.view_and_scenepoint2global, pfu, nv)
-            exch = carry.pop("exch", None) if carry is not None else None
-            rows = {"own": carry.pop("rows_own")} if exch is not None else None
-            glob = self.view_and_scenepoint2global.forward_plan(
-                view, pts, plans["view2global"], plans["scenepoint2global"], prev_glob,
-                plans.get("_partial", {}).get("scenepoint2global"), plans.get("_shard"),
-                xl_pts=carry.pop("XLs2g", None) if carry is not None else None,
-                xl_view=carry.pop("XLv2g", None) if carry is not None else None, pre_glob=pre_glob,
-                plan_v2g_partial=plans.get("_partial", {}).get("view2global"), chain=chain, exch=exch, rows=rows)
+            part = plans.get("_partial", {})
+            glob, rows = self.view_and_scenepoint2global.forward_plan(
+                view, pts, plans["view2global"], plans["scenepoint2global"], prev_glob, part.get("scenepoint2global"),
+                plans.get("_shard"), part.get("view2global"), chain, carry)
             if rows is not None:
-                carry.update(SV=rows["SV"], XRc=rows["XRc"])
-            if isinstance(glob, tuple):  # GlobalChainFn: g with its consumers' rows
-                if len(glob) == 4:
-                    glob, SG, XRv, XRp = glob
-                    carry.update(SG=SG, pre_glob=(XRv, XRp, glob))
-                else:
-                    glob, SG = glob
-                    carry.update(SG=SG)
-            elif carry is not None and nxt is not None and getattr(nxt, "output_global", False) \
-                    and dense._gvec_ok(glob, glob.shape[1]):
-                hg = dense.global_hub_params(pfu, nxt.view_and_scenepoint2global)
+                carry.SV, carry.XRc = rows
+            if isinstance(glob, tuple):  # GlobalChainFn: (g, SG[, XRv, XRp]), g with its consumers' rows
+                glob, carry.SG, *xr = glob
+                carry.pre_glob = (*xr, glob) if xr else None
+            elif carry is not None and nv is not None and dense._gvec_ok(glob, glob.shape[1]):
+                hg = dense.global_hub_params(pfu, nv)
                 if hg is not None:
-                    skip, SG, XRv, XRp = dense.GlobalHubFn.apply(glob, *hg)
-                    carry.update(SG=SG, pre_glob=(XRv, XRp, skip))
+                    skip, carry.SG, XRv, XRp = dense.GlobalHubFn.apply(glob, *hg)
+                    carry.pre_glob = (XRv, XRp, skip)
         if self.global2view_and_global2scenepoint_enabled:
             pts = self.global2scenepoint(glob, pts)
             view = self.global2view(glob, view)
         return pts, view, glob
+
+
+class EdgeCamAttend:
+    """attend callback of gfu.forward_fused: EdgeCamFn on P (lin_l of both convs, the camera
+    attention; XLp written in point order) then the point attention on XLp.  The call sets .P, the
+    block's input rows (P, or the output of a PendingEpilogue P), and .token, the prologue's (see
+    EdgePrologueFn).  dwp: EdgeCamFn's, it returns the block's lin_proj gradient (P0: its skip input)."""
+
+    def __init__(self, gfu, P, ln_w, ln_b, eps, Wp, plans, P0=None, dwp=False):
+        (Wpt, bpt), (Wc, bc) = gfu.lin_l_pair()
+        self.P, self.token, self.pp, self.cp = P, None, plans["proj2scenepoint"], gfu.proj2scenepoint.graph_conv
+        cc = gfu.proj2view.graph_conv
+        self.cam = CamArgs(ln_w=ln_w, ln_b=ln_b, Wpt=Wpt, bpt=bpt, Wc=Wc, bc=bc, Wp=Wp, eps=eps, pos=self.pp.pos,
+                           XR=None, att=cc.att, bias=cc.bias, plan=plans["proj2view"], heads=cc.heads,
+                           slope=cc.negative_slope, plan_partial=plans.get("_partial", {}).get("proj2view"),
+                           shard=plans.get("_shard"), P0=P0, dwp=dwp)
+
+    def __call__(self, XRp, XRc):
+        pp, cp, cam = self.pp, self.cp, self.cam._replace(XR=XRc)
+        if isinstance(self.P, PendingEpilogue) and self.P.block0 and cam.ln_w is None:
+            self.P = self.P.materialize()  # the block-0 seam is built for a LayerNorm prologue only
+        if isinstance(self.P, PendingEpilogue):  # the previous block's epilogue in the same kernel
+            self.P, XLp, agg_c, self.token = self.P.seam(cam)
+        else:
+            XLp, agg_c, self.token = EdgeCamFn.apply(self.P, *cam)
+        agg_p = GatAttentionFn.apply(XLp, XRp, cp.att, cp.bias, pp, cp.heads, cp.negative_slope,
+                                     pp.pos is not None)[0]
+        return agg_p, agg_c
 
 
 class GraphAttnSfMProjectionFeatureUpdate(Module):
@@ -718,63 +722,42 @@ class GraphAttnSfMLayer(Module):
     def forward_fused0(self, P, plans, edges, carry=None, nxt=None):
         """Block 0 (2-wide inputs, projected residual) with the block-0 HIP edge kernels."""
         la, lb = self.prev_projfeat_norm_layer, self.residual_skipconn_proj_norm_layer
-        gfu = self.global_feature_update
-        pfu = self.projection_feature_update
+        gfu, pfu = self.global_feature_update, self.projection_feature_update
         W, b = gfu.lin_l_stack()
         pp = plans["proj2scenepoint"]
-        pos = pp.pos
-        perm = pp.perm if pos is not None and pp.src_rows == pp.num_edges else None
-        XL, token = Block0PrologueFn.apply(P.contiguous(), la.weight, la.bias, W, b, la.eps, pos, perm)
-        pts, view, glob = gfu.forward_fused(XL, plans, None, None, None, xl_sorted=pos is not None, carry=carry,
-                                            pfu=pfu, nxt=nxt)
-        sp, sv, sg = pfu.node_terms(pts, view, glob, *((carry.pop("SA", None), carry.pop("SV", None),
-                                                          carry.pop("SG", None))
-                                                         if carry is not None else (None, None, None)))
-        sv, sg = _wrap_boundary(plans.get("_shard"), sv, sg, carry)
-        sv, sg = _fold_global(sv, sg, plans)
+        perm = pp.perm if pp.pos is not None and pp.src_rows == pp.num_edges else None
+        XL, token = Block0PrologueFn.apply(P.contiguous(), la.weight, la.bias, W, b, la.eps, pp.pos, perm)
+        pts, view, glob = gfu.forward_fused(XL, plans, carry=carry, pfu=pfu, nxt=nxt)
+        sp, sv, sg = _edge_terms(pfu, pts, view, glob, plans, carry)
         sk = self.skip_projection.lin_proj
-        args = (P.contiguous(), token, sp, sv, sg, pfu.lin_proj.weight, pfu.lin_proj.bias, la.weight, la.bias,
-                lb.weight, lb.bias, sk.weight, sk.bias, la.eps, edges)
-        if EDGE_SEAM and EDGE_SEAM0 and _seam0_ok(args):  # run with block 1's prologue (edge_block.Seam0Fn)
-            return PendingEpilogue(args, block0=True), pts, view, glob
-        return Block0EpilogueFn.apply(*args), pts, view, glob
+        epi = PendingEpilogue(Epilogue0Args(P.contiguous(), token, sp, sv, sg, pfu.lin_proj.weight, pfu.lin_proj.bias,
+                                            la.weight, la.bias, lb.weight, lb.bias, sk.weight, sk.bias, la.eps, edges))
+        # left pending, it runs with block 1's prologue (edge_block.Seam0Fn)
+        return (epi if EDGE_SEAM and EDGE_SEAM0 and epi.seam_ok() else epi.materialize()), pts, view, glob
 
     def forward_fused(self, P, plans, edges, prev_pt, prev_view, prev_glob, P0, carry=None, nxt=None):
         """Blocks >= 1 with the fused HIP edge kernels (see gasfm_amd/edge_block.py).  P may be the
         previous block's PendingEpilogue; with EDGE_SEAM this block's own epilogue is returned
         pending as well (the caller's next consumer runs or materializes it)."""
         ln = self.prev_projfeat_norm_layer
-        gfu = self.global_feature_update
-        pfu = self.projection_feature_update
-        pos = plans["proj2scenepoint"].pos
+        gfu, pfu = self.global_feature_update, self.projection_feature_update
         P0e = P0 if self.add_skipconn_from_init_projfeat else None
         dwp = False
         if gfu.cam_fusable(plans):
-            holder = {}
             # the block's lin_proj gradient from its edge_cam_pbwd (edge_block.EPI_FOLD)
             dwp = edge_block.EPI_FOLD and ln.weight is not None
-            attend = gfu.edge_cam_attend(P, ln.weight, ln.bias, ln.eps, pfu.lin_proj.weight, plans, holder,
-                                         P0e if dwp else None, dwp)
-            pts, view, glob = gfu.forward_fused(None, plans, prev_pt, prev_view, prev_glob, carry=carry, pfu=pfu,
-                                                nxt=nxt, attend=attend)
-            token = holder["token"]
-            P = holder["P"]
+            attend = EdgeCamAttend(gfu, P, ln.weight, ln.bias, ln.eps, pfu.lin_proj.weight, plans,
+                                   P0e if dwp else None, dwp)
+            pts, view, glob = gfu.forward_fused(None, plans, prev_pt, prev_view, prev_glob, carry, pfu, nxt, attend)
+            P, token = attend.P, attend.token
         else:
             P = materialize(P)
-            (W, b), (W2, b2) = gfu.lin_l_pair()
-            XL, token = EdgePrologueFn.apply(P, ln.weight, ln.bias, W, b, pfu.lin_proj.weight, ln.eps, pos, W2, b2)
-            pts, view, glob = gfu.forward_fused(XL, plans, prev_pt, prev_view, prev_glob, xl_sorted=pos is not None,
-                                                carry=carry, pfu=pfu, nxt=nxt)
-        sp, sv, sg = pfu.node_terms(pts, view, glob, *((carry.pop("SA", None), carry.pop("SV", None),
-                                                          carry.pop("SG", None))
-                                                         if carry is not None else (None, None, None)))
-        sv, sg = _wrap_boundary(plans.get("_shard"), sv, sg, carry)
-        sv, sg = _fold_global(sv, sg, plans)
-        args = (P, P0e, token, sp, sv, sg, pfu.lin_proj.weight, pfu.lin_proj.bias, ln.weight, ln.bias, ln.eps, edges,
-                dwp)
-        if EDGE_SEAM and _seam_ok(args):
-            return PendingEpilogue(args), pts, view, glob
-        return EdgeEpilogueFn.apply(*args), pts, view, glob
+            XL, token = gfu.prologue(P, plans, ln, pfu.lin_proj.weight)
+            pts, view, glob = gfu.forward_fused(XL, plans, prev_pt, prev_view, prev_glob, carry, pfu, nxt)
+        sp, sv, sg = _edge_terms(pfu, pts, view, glob, plans, carry)
+        epi = PendingEpilogue(EpilogueArgs(P, P0e, token, sp, sv, sg, pfu.lin_proj.weight, pfu.lin_proj.bias, ln.weight,
+                                           ln.bias, ln.eps, edges, dwp))
+        return (epi if EDGE_SEAM and epi.seam_ok() else epi.materialize()), pts, view, glob
 
     def forward_plan(self, P, plans, edges, prev_pt=None, prev_view=None, prev_glob=None, P0=None, carry=None,
                      nxt=None):
@@ -782,14 +765,12 @@ class GraphAttnSfMLayer(Module):
 
         carry / nxt: see GraphAttnSfMGlobalFeatureUpdate.forward_fused (fused CUDA path only).  On
         the fused path P and P' may be PendingEpilogue handles (edge_block.SeamFn)."""
-        if isinstance(P, PendingEpilogue) and self.fusable():
+        if (isinstance(P, PendingEpilogue) or P.is_cuda) and self.fusable():
             return self.forward_fused(P, plans, edges, prev_pt, prev_view, prev_glob, P0, carry, nxt)
         P = materialize(P)
-        if P.is_cuda and self.fusable():
-            return self.forward_fused(P, plans, edges, prev_pt, prev_view, prev_glob, P0, carry, nxt)
         if P.is_cuda and prev_pt is None and prev_view is None and prev_glob is None and self.fusable0():
             return self.forward_fused0(P, plans, edges, carry, nxt)
-        if carry:
+        if carry is not None and carry.pending():
             raise RuntimeError("point hub outputs pending for a block on the unfused path")
         if self.use_norm_proj_update:
             P_hat = edge_ops.layer_norm_relu(P, self.prev_projfeat_norm_layer)
@@ -1101,6 +1082,8 @@ class GraphAttnSfMNet(BaseNet):
     def edge_index_for(self, data, device):
         return scene_edge_index(data, device)
 
+    last_carry = None  # the last forward's BlockCarry: the tests read that nothing stays pending in it
+
     def forward_features(self, values, edges):
         """Block stack + final update on raw tensors; returns (P, pts, view) after the final update."""
         plans = edges.plans
@@ -1118,34 +1101,30 @@ class GraphAttnSfMNet(BaseNet):
         heads = self.view_head_enabled or self.scenepoint_head_enabled
         fgu = self.final_global_update if heads else None
         final_fused = fgu is not None and values.is_cuda and fgu.fusable() and self.equivariant_blocks[-1].fusable()
-        # consumers of each block's node outputs (PointHubFn, ViewHubFn): the next block's (or
-        # the fused final update's) Proj2ScenePoint / Proj2View; carry hands the hub outputs forward
-        carry = {} if (values.is_cuda and sf) else None
+        # nxt, the consumers of each block's hub outputs: the next block's (or the fused final update's)
+        # Proj2ScenePoint / Proj2View; carry hands them forward
+        carry = self.last_carry = BlockCarry() if (values.is_cuda and sf) else None
         blocks = list(self.equivariant_blocks)
         for i, blk in enumerate(blocks):
             if i + 1 < len(blocks):
                 nxt = blocks[i + 1].global_feature_update if blocks[i + 1].fusable() else None
             else:
                 nxt = fgu if final_fused else None
-            P, pts, view, glob = blk.forward_plan(P, plans, edges, pts if sf else None, view if sf else None,
-                                                  glob if sf else None, P0=p0s[i], carry=carry, nxt=nxt)
+            prev = (pts, view, glob) if sf else (None, None, None)
+            P, pts, view, glob = blk.forward_plan(P, plans, edges, *prev, P0=p0s[i], carry=carry, nxt=nxt)
         if heads:
-            args = (pts if sf else None, view if sf else None, glob if sf else None)
+            args = (pts, view, glob) if sf else (None, None, None)
             pend = isinstance(P, PendingEpilogue)
             if (pend or P.is_cuda) and fgu.fusable() and fgu.cam_fusable(plans) and (pend or P.shape[1] == 32):
                 # raw (un-normalised) projection features (graph_attn_sfm.py:141-148): no LN prologue;
                 # a pending last-block epilogue runs in the same kernel (SeamFn)
-                holder = {}
-                attend = fgu.edge_cam_attend(P if pend else P.contiguous(), None, None, 1e-5, None, plans, holder)
+                attend = EdgeCamAttend(fgu, P if pend else P.contiguous(), None, None, 1e-5, None, plans)
                 pts, view, _ = fgu.forward_fused(None, plans, *args, carry=carry, attend=attend)
-                P = holder["P"]
+                P = attend.P
             else:
                 P = materialize(P)
                 if P.is_cuda and P.shape[1] == 32 and fgu.fusable():
-                    pos = plans["proj2scenepoint"].pos
-                    (W, b), (W2, b2) = fgu.lin_l_pair()
-                    XL, _ = EdgePrologueFn.apply(P.contiguous(), None, None, W, b, None, 1e-5, pos, W2, b2)
-                    pts, view, _ = fgu.forward_fused(XL, plans, *args, xl_sorted=pos is not None, carry=carry)
+                    pts, view, _ = fgu.forward_fused(fgu.prologue(P.contiguous(), plans)[0], plans, *args, carry=carry)
                 else:
                     pts, view, _ = fgu.forward_plan(P, plans, *args)
         return materialize(P), pts, view

@@ -199,6 +199,8 @@ def _worker_sharded_model(rank, world, port, q, cameras=False, bounds=None, max_
         cP = torch.randn((sc.m, 3, 4), generator=g).to(dev)
         cX = torch.randn((4, sc.n), generator=g).to(dev)
         pred = model(data)
+        # every hub output handed between the blocks was consumed (point- and camera-sharded alike)
+        assert net.last_carry is not None and net.last_carry.pending() == []
         loss = (pred["Ps_norm"] * cP).sum() + (pred["pts3D"] * cX[:, data.point_slice]).sum()
         loss.backward()
         model.sync_grads()

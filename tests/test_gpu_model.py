@@ -43,6 +43,8 @@ def test_net_small_forward_backward(device):
     net.load_state_dict(sd)
     net = net.to(device)
     pred = net(data)
+    # every hub output handed between the blocks (model.BlockCarry) was consumed
+    assert net.last_carry is not None and net.last_carry.pending() == []
     np.testing.assert_allclose(pred["Ps_norm"].detach().cpu().numpy(), f["Ps_norm"], atol=OUT_ATOL, rtol=OUT_RTOL)
     np.testing.assert_allclose(pred["pts3D"].detach().cpu().numpy(), f["pts3D"], atol=OUT_ATOL, rtol=OUT_RTOL)
     loss = (pred["Ps_norm"] * torch.from_numpy(f["cP"]).float().to(device)).sum() + \
