@@ -143,6 +143,13 @@ _SIGS = {
     "gasfm_scene_emit": (_i32, [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gasfm_scene_point_csr": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "gasfm_scene_homography": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gasfm_scene_shard_bounds": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "gasfm_scene_shard_cam_range": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "gasfm_scene_shard_stats": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "gasfm_scene_shard_emit": (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp]),
+    "gasfm_scene_shard_point_csr": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
+                                           _vp]),
     "gasfm_outlier_counts": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "gasfm_outlier_mark": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "gasfm_outlier_moments": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -1902,6 +1909,97 @@ def scene_build(M, Ns=None):
     cam_ptr = tile_base[0::T // m].contiguous() if T else torch.zeros(m + 1, **i32)
     return {"cam": cam, "pt": pt, "values": vals, "pt_count": pt_count, "cam_ptr": cam_ptr, "pt_ptr": pt_ptr,
             "perm": perm, "pos": pos}
+
+
+# ---------------------------------------------------------------- point shard of a device scene (scene_shard.hip)
+def _edge_ids(t, name, what):
+    """(tensor, is64) of a per-edge int32 / int64 CUDA index vector."""
+    if not t.is_cuda or t.dtype not in (torch.int32, torch.int64) or t.dim() != 1 or not t.is_contiguous():
+        raise TypeError(f"{what}: {name} must be a contiguous int32 or int64 CUDA vector")
+    return t, int(t.dtype == torch.int64)
+
+
+def scene_shard_bounds(pt_ptr, world):
+    """distributed.partition_points over the point CSR: int32 [world + 1] device boundaries."""
+    _dev_check("scene_shard_bounds", ("pt_ptr", pt_ptr, torch.int32))
+    if world < 1 or pt_ptr.dim() != 1 or pt_ptr.shape[0] < 1:
+        raise ValueError("scene_shard_bounds: world >= 1 and pt_ptr [n + 1]")
+    bounds = torch.empty(world + 1, dtype=torch.int32, device=pt_ptr.device)
+    check(lib().gasfm_scene_shard_bounds(_p(pt_ptr), pt_ptr.shape[0] - 1, world, _p(bounds), _stream(pt_ptr)),
+          "gasfm_scene_shard_bounds")
+    return bounds
+
+
+def scene_shard_ranges(cam_ptr, pt_ptr, pt, bounds, rank, c0=0, c1=0):
+    """The per-camera runs of rank ``rank``'s points (bounds: int32 device boundaries) and the scalars
+    the host sizes the shard by: dict lo, count (int32 [m]), lcam_ptr (int32 [m + 1]), pts_per_cam
+    (int64 [m]), valid_view (bool [m]), stats (int64 [9], gasfm_scene_shard_stats)."""
+    what = "scene_shard_ranges"
+    _dev_check(what, ("cam_ptr", cam_ptr, torch.int32), ("pt_ptr", pt_ptr, torch.int32), ("bounds", bounds, torch.int32))
+    pt, is64 = _edge_ids(pt, "pt", what)
+    m, n = cam_ptr.shape[0] - 1, pt_ptr.shape[0] - 1
+    if m < 0 or n < 0 or not 0 <= rank < bounds.shape[0] - 1 or not 0 <= c0 <= c1 <= m:
+        raise ValueError(f"{what}: rank {rank} of {bounds.shape[0] - 1}, cameras [{c0}, {c1}) of {m}")
+    dev = cam_ptr.device
+    L, st = lib(), _stream(cam_ptr)
+    lo = torch.empty(m, dtype=torch.int32, device=dev)
+    count = torch.empty(m, dtype=torch.int32, device=dev)
+    ppc = torch.empty(m, dtype=torch.int64, device=dev)
+    vv = torch.empty(m, dtype=torch.uint8, device=dev)
+    stats = torch.empty(9, dtype=torch.int64, device=dev)
+    check(L.gasfm_scene_shard_cam_range(_p(cam_ptr), _p(pt), is64, m, _p(bounds), rank, _p(lo), _p(count), _p(ppc),
+                                        _p(vv), st), "gasfm_scene_shard_cam_range")
+    check(L.gasfm_scene_shard_stats(_p(cam_ptr), m, _p(pt_ptr), n, _p(bounds), rank, c0, c1, _p(stats), st),
+          "gasfm_scene_shard_stats")
+    return {"lo": lo, "count": count, "lcam_ptr": scan_i32(count), "pts_per_cam": ppc, "valid_view": vv.view(torch.bool),
+            "stats": stats}
+
+
+def scene_shard_emit(r, pt, p0, E_loc, sources):
+    """The local edges of scene_shard_ranges' result r: (sel int64 [E_loc], indices int64 [2, E_loc],
+    cam32, pt32 int32 [E_loc], [the gathered rows of each [E, 2] fp32 array in ``sources`` (<= 3)])."""
+    what = "scene_shard_emit"
+    pt, is64 = _edge_ids(pt, "pt", what)
+    if len(sources) > 3:
+        raise ValueError(f"{what}: at most three source arrays")
+    for s in sources:
+        if not s.is_cuda or s.dtype != torch.float32 or s.dim() != 2 or s.shape != (pt.shape[0], 2) \
+                or not s.is_contiguous():
+            raise TypeError(f"{what}: sources must be contiguous float32 CUDA [E, 2] arrays")
+    dev = pt.device
+    m = r["lo"].shape[0]
+    sel = torch.empty(E_loc, dtype=torch.int64, device=dev)
+    indices = torch.empty((2, E_loc), dtype=torch.int64, device=dev)
+    cam32 = torch.empty(E_loc, dtype=torch.int32, device=dev)
+    pt32 = torch.empty(E_loc, dtype=torch.int32, device=dev)
+    dst = [torch.empty((E_loc, 2), dtype=torch.float32, device=dev) for _ in sources]
+    sp = [_p(s) for s in sources] + [None] * (3 - len(sources))
+    dp = [_p(d) for d in dst] + [None] * (3 - len(dst))
+    check(lib().gasfm_scene_shard_emit(_p(r["lcam_ptr"]), _p(r["lo"]), m, _p(pt), is64, E_loc, p0, sp[0], sp[1], sp[2],
+                                       _p(sel), _p(indices), _p(cam32), _p(pt32), dp[0], dp[1], dp[2], _stream(pt)),
+          "gasfm_scene_shard_emit")
+    return sel, indices, cam32, pt32, dst
+
+
+def scene_shard_point_csr(r, pt_ptr, perm, cam, p0, p1, E_loc):
+    """The local point CSR of scene_shard_ranges' result r: (lpt_ptr int32 [n_loc + 1], cam_per_pts
+    int64 [n_loc], valid_pt bool [n_loc], perm, pos int32 [E_loc]).  perm: the global CSR's, or None."""
+    what = "scene_shard_point_csr"
+    _dev_check(what, ("pt_ptr", pt_ptr, torch.int32), ("perm", perm, torch.int32))
+    cam, is64 = _edge_ids(cam, "cam", what)
+    n_loc = p1 - p0
+    if not 0 <= p0 <= p1 < pt_ptr.shape[0] or (perm is not None and perm.shape[0] != cam.shape[0]):
+        raise ValueError(f"{what}: points [{p0}, {p1}) of {pt_ptr.shape[0] - 1}; perm must have one entry per edge")
+    dev = cam.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    lpt_ptr = torch.empty(n_loc + 1, **i32)
+    cpp = torch.empty(n_loc, dtype=torch.int64, device=dev)
+    vp = torch.empty(n_loc, dtype=torch.uint8, device=dev)
+    lperm, lpos = torch.empty(E_loc, **i32), torch.empty(E_loc, **i32)
+    check(lib().gasfm_scene_shard_point_csr(_p(pt_ptr), _p(perm), _p(cam), is64, _p(r["lcam_ptr"]), _p(r["lo"]), p0,
+                                            n_loc, E_loc, _p(lpt_ptr), _p(cpp), _p(vp), _p(lperm), _p(lpos),
+                                            _stream(cam)), "gasfm_scene_shard_point_csr")
+    return lpt_ptr, cpp, vp.view(torch.bool), lperm, lpos
 
 
 def sum_n(tensors):

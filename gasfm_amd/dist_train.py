@@ -25,7 +25,8 @@ it with one all-reduce).  Then per rank:
 
 ``StaticTrainer`` (static_batch.py) is the single-GPU captured form of the same step; this module is
 its point-sharded counterpart, run eagerly: the shard's plans are rebuilt per sampled scene on the
-host from one device-to-host copy of the scene's edges.
+host from one device-to-host copy of the scene's edges, or -- ``ShardedTrainer(device_shard=True)`` -- on
+the device by shard_device.shard_scene_on_device, which returns equal shards.
 """
 import copy
 
@@ -37,6 +38,7 @@ from . import _native
 from .distributed import ShardContext, ShardedGraphAttnSfMNet, shard_scene
 from .evaluation import _pixel_cameras, _pixel_measurements
 from .scene import SparseMat
+from .shard_device import shard_scene_on_device
 
 
 class _HostEdges:
@@ -110,9 +112,12 @@ class ShardedTrainer:
     net: this rank's GraphAttnSfMNet (same initial weights on every rank); lossf: ESFMLoss;
     optimizer: stepped after sync_grads (gasfm_amd.optim.Adam keeps the ranks bitwise in step).
     group: the process group (default: the world); world / rank from it unless ``emulate_world``
-    (one GPU standing in for rank 0 of that many: collectives become local copies, timing only)."""
+    (one GPU standing in for rank 0 of that many: collectives become local copies, timing only).
+    device_shard: build the shard with shard_device.shard_scene_on_device (kernels over the scene's device
+    arrays, two small host reads) instead of shard_device_scene's host round trip; the shards are equal."""
 
-    def __init__(self, net, lossf, optimizer=None, group=None, cameras=False, emulate_world=0, verify=False):
+    def __init__(self, net, lossf, optimizer=None, group=None, cameras=False, emulate_world=0, verify=False,
+                 device_shard=False):
         self.net, self.lossf, self.optimizer = net, lossf, optimizer
         self.group = group
         self.cameras = cameras
@@ -124,6 +129,7 @@ class ShardedTrainer:
         self.model = ShardedGraphAttnSfMNet(net, group=group, cameras=cameras)
         self.params = [p for p in net.parameters() if p.requires_grad]
         self.verify = verify
+        self.device_shard = bool(device_shard)
         self.last = None  # (net shard, loss shard) of the last step
 
     def _check_same_scene(self, *scenes):
@@ -148,8 +154,9 @@ class ShardedTrainer:
         inputs = data if inputs is None else inputs
         if self.verify:
             self._check_same_scene(data, inputs)
-        net_shard, loss_shard = shard_device_scene(data, self.rank, self.world, inputs, cameras=self.cameras,
-                                                   emulate=self.emulate_world > 1)
+        shard = shard_scene_on_device if self.device_shard else shard_device_scene
+        net_shard, loss_shard = shard(data, self.rank, self.world, inputs, cameras=self.cameras,
+                                      emulate=self.emulate_world > 1)
         self.last = (net_shard, loss_shard)
         for p in self.params:
             p.grad = None

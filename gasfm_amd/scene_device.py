@@ -122,16 +122,18 @@ def _plan(seg_ptr, perm, pos, num_targets, num_edges, src_rows, max_piece, tag, 
     return plan
 
 
-def _star_source_plan(src, src_rows, max_piece, tag, ident=None):
+def _star_source_plan(src, src_rows, max_piece, tag, ident=None, all_partial=False):
     """One-target plan over source rows ``src`` (the global graphs): perm = src unless identity
-    (ident: that test's answer when the caller read it already)."""
+    (ident: that test's answer when the caller read it already).  all_partial: the exchange form of
+    a point shard (distributed.shard_scene's partial plans)."""
     k = int(src.shape[0])
     dev = src.device
     seg_ptr = torch.tensor([0, k], dtype=torch.int32, device=dev)
     if ident is None:
         ident = k == 0 or bool(torch.equal(src, torch.arange(k, device=dev, dtype=src.dtype)))
     perm = None if ident else src.to(torch.int32).contiguous()
-    return _plan(seg_ptr, perm, None, 1, k, src_rows, max_piece, tag, counts=_piece_counts_host([k], max_piece))
+    return _plan(seg_ptr, perm, None, 1, k, src_rows, max_piece, tag, all_partial=all_partial,
+                 counts=_piece_counts_host([k], max_piece))
 
 
 def graph_wrappers_device(b, m, n, max_piece=None):

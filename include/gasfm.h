@@ -1097,6 +1097,50 @@ int gasfm_scene_homography(const float* M, int64_t ldM, int32_t m, int32_t n, co
                            const uint64_t* pt_valid, const float* Ns, const float* R, const float* Ninv,
                            float* out, int64_t ldO, void* stream);
 
+/* ---- a rank's point shard of a device scene (scene_shard.hip) -----------
+ * distributed.shard_scene on the device: the edges of the contiguous point range [p0, p1) of a
+ * cam-major scene (cam_ptr [m+1]; stable point CSR pt_ptr [n+1] with perm slot -> edge, NULL =
+ * identity; cam / pt per edge, int32 or int64 as the *_is64 flag says), re-indexed to local points.
+ * Integer and copy kernels without atomics: deterministic.  E < 2^31. */
+
+/* distributed.partition_points: bounds[r] (r = 1 .. world-1) = the smallest i with
+ * pt_ptr[i] * world >= E * r in 64-bit integers (E = pt_ptr[n]), bounds[0] = 0, bounds[world] = n. */
+int gasfm_scene_shard_bounds(const int32_t* pt_ptr, int32_t n, int32_t world, int32_t* bounds, void* stream);
+
+/* Per camera c, with [p0, p1) = bounds[rank], bounds[rank + 1] read on the device: lo[c] = its first
+ * edge with pt >= p0 and count[c] = its edges with pt in [p0, p1) (one contiguous run: points ascend
+ * inside a camera); pts_per_cam [m] = count as int64; valid_view [m] = 1 where the camera has >=
+ * MIN_N_POINTS_PER_VIEW edges in the whole scene. */
+int gasfm_scene_shard_cam_range(const int32_t* cam_ptr, const void* pt, int32_t pt_is64, int32_t m,
+                                const int32_t* bounds, int32_t rank, int32_t* lo, int32_t* count,
+                                int64_t* pts_per_cam, uint8_t* valid_view, void* stream);
+
+/* The scalars the host sizes the shard by, out[9]: p0, p1, E_loc = pt_ptr[p1] - pt_ptr[p0], then
+ * (count, first invalid index relative to the range's start or the range's length) of the valid views
+ * of [0, m), of those in the own camera rows [c0, c1), and of the valid points (>=
+ * MIN_N_VIEWS_PER_POINT views) of [p0, p1).  One workgroup. */
+int gasfm_scene_shard_stats(const int32_t* cam_ptr, int32_t m, const int32_t* pt_ptr, int32_t n,
+                            const int32_t* bounds, int32_t rank, int32_t c0, int32_t c1, int64_t* out,
+                            void* stream);
+
+/* The E_loc local edges, cam-major: local edge j of camera c (lcam_ptr [m+1] = exclusive scan of
+ * count) is global edge sel[j] = lo[c] + j - lcam_ptr[c].  indices [2 x E_loc] int64 = (c, pt - p0),
+ * cam32 / pt32 the same as int32, dst_k[j] = src_k[sel[j]] for up to three [E x 2] fp32 arrays (bit
+ * copies; a NULL src_k is skipped; rows 8-byte aligned). */
+int gasfm_scene_shard_emit(const int32_t* lcam_ptr, const int32_t* lo, int32_t m, const void* pt, int32_t pt_is64,
+                           int64_t E_loc, int32_t p0, const float* src0, const float* src1, const float* src2,
+                           int64_t* sel, int64_t* indices, int32_t* cam32, int32_t* pt32, float* dst0, float* dst1,
+                           float* dst2, void* stream);
+
+/* The local point CSR: lpt_ptr [n_loc+1] = pt_ptr[p0 + q] - pt_ptr[p0], cam_per_pts [n_loc] (int64)
+ * its differences, valid_pt [n_loc] = 1 where >= MIN_N_VIEWS_PER_POINT, and lperm[k] = the local id
+ * lcam_ptr[c] + g - lo[c] of the global edge g (camera c) at point-order position pt_ptr[p0] + k,
+ * lpos[lperm[k]] = k: equal to gasfm_build_csr on the local edges' points. */
+int gasfm_scene_shard_point_csr(const int32_t* pt_ptr, const int32_t* perm, const void* cam, int32_t cam_is64,
+                                const int32_t* lcam_ptr, const int32_t* lo, int32_t p0, int32_t n_loc,
+                                int64_t E_loc, int32_t* lpt_ptr, int64_t* cam_per_pts, uint8_t* valid_pt,
+                                int32_t* lperm, int32_t* lpos, void* stream);
+
 /* dst[i] = src[0][i] + ... + src[n-1][i] (index order), n <= 16, count % 4 == 0, 16-byte aligned
  * rows: the gradient of a tensor with n consumers in one pass (the embedded projection input P0
  * feeds every block's projection update, layers.py:245-251; autograd would add n-1 times). */
