@@ -150,6 +150,11 @@ _SIGS = {
                                       _vp, _vp, _vp]),
     "gasfm_scene_shard_point_csr": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
                                            _vp]),
+    "gasfm_depth_part_slots": (_i64, [_i64]),
+    "gasfm_depth_targets": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "gasfm_depth_gather": (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i64, _vp,
+                                  _vp, _vp, _vp]),
+    "gasfm_depth_rescale": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "gasfm_outlier_counts": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "gasfm_outlier_mark": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "gasfm_outlier_moments": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -2000,6 +2005,83 @@ def scene_shard_point_csr(r, pt_ptr, perm, cam, p0, p1, E_loc):
                                             n_loc, E_loc, _p(lpt_ptr), _p(cpp), _p(vp), _p(lperm), _p(lpos),
                                             _stream(cam)), "gasfm_scene_shard_point_csr")
     return lpt_ptr, cpp, vp.view(torch.bool), lperm, lpos
+
+
+# ---------------------------------------------------------------- per-edge depth targets (depth_targets.hip)
+def _depth_edges(what, cam, pt):
+    cam, is64 = _edge_ids(cam, "cam", what)
+    pt, pis64 = _edge_ids(pt, "pt", what)
+    if is64 != pis64 or cam.shape != pt.shape:
+        raise TypeError(f"{what}: cam and pt must have one dtype and one length")
+    return cam, pt, is64
+
+
+def _depth_part(E, dev):
+    """(per-wave count scratch, the [1] int32 count) of a depth_targets.hip kernel over E edges."""
+    part = torch.empty(int(lib().gasfm_depth_part_slots(E)), dtype=torch.int32, device=dev)
+    return part, torch.zeros(1, dtype=torch.int32, device=dev)
+
+
+def depth_targets(a, X, cam, pt, out=None):
+    """d[e] = a[cam[e]] . X[pt[e]] (gasfm_depth_targets): (d [E] float32, bad [1] int32 = the number of
+    edges whose depth is not finite or not > 0, on the device).  a [m, 4], X [n, 4] float32."""
+    what = "depth_targets"
+    cam, pt, is64 = _depth_edges(what, cam, pt)
+    for t, name in ((a, "a"), (X, "X")):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 4 or not t.is_contiguous():
+            raise TypeError(f"{what}: {name} must be a contiguous float32 CUDA [rows, 4] tensor")
+    E = cam.shape[0]
+    d = torch.empty(E, dtype=torch.float32, device=cam.device) if out is None else out
+    _dev_check(what, ("out", d, torch.float32))
+    if d.shape != (E,):
+        raise ValueError(f"{what}: out must have one entry per edge")
+    part, bad = _depth_part(E, cam.device)
+    check(lib().gasfm_depth_targets(_p(a), a.shape[0], _p(X), X.shape[0], _p(cam), _p(pt), is64, E, _p(d), _p(part),
+                                    _p(bad), _stream(cam)), "gasfm_depth_targets")
+    return d, bad
+
+
+def depth_gather(pcam_ptr, ppt, pd, view_idx, keep, cam, pt, out=None):
+    """The sampled scene's per-edge depths from its parent's (gasfm_depth_gather): (d [E] float32,
+    missing [1] int32 = the number of sampled edges without a parent edge, on the device)."""
+    what = "depth_gather"
+    cam, pt, is64 = _depth_edges(what, cam, pt)
+    ppt, pis64 = _edge_ids(ppt, "parent pt", what)
+    _dev_check(what, ("parent cam_ptr", pcam_ptr, torch.int32), ("parent depths", pd, torch.float32),
+               ("view_idx", view_idx, torch.int64), ("keep", keep, torch.int64))
+    if pcam_ptr.dim() != 1 or pcam_ptr.shape[0] < 1 or pd.shape != ppt.shape or view_idx.dim() != 1 or keep.dim() != 1:
+        raise ValueError(f"{what}: parent cam_ptr [m + 1], parent pt / depths [E], view_idx [m'], keep [n']")
+    E = cam.shape[0]
+    d = torch.empty(E, dtype=torch.float32, device=cam.device) if out is None else out
+    _dev_check(what, ("out", d, torch.float32))
+    if d.shape != (E,):
+        raise ValueError(f"{what}: out must have one entry per edge")
+    part, missing = _depth_part(E, cam.device)
+    check(lib().gasfm_depth_gather(_p(pcam_ptr), _p(ppt), pis64, _p(pd), pcam_ptr.shape[0] - 1, ppt.shape[0],
+                                   _p(view_idx), _p(keep), view_idx.shape[0], keep.shape[0], _p(cam), _p(pt), is64, E,
+                                   _p(d), _p(part), _p(missing), _stream(cam)), "gasfm_depth_gather")
+    return d, missing
+
+
+def depth_rescale(d, cam, pt, M, Ns, R, out=None):
+    """d[e] / z_old * z_new of the rotational homography augmentation (gasfm_depth_rescale), the old
+    pixel measurements read from the un-augmented dense M [2m, n]."""
+    what = "depth_rescale"
+    _check_M(M, what)
+    cam, pt, is64 = _depth_edges(what, cam, pt)
+    m, n = M.shape[0] // 2, M.shape[1]
+    for t, name in ((Ns, "Ns"), (R, "R")):
+        if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (m, 3, 3) or not t.is_contiguous():
+            raise TypeError(f"{what}: {name} must be a contiguous float32 CUDA [m, 3, 3] tensor")
+    _dev_check(what, ("d", d, torch.float32))
+    E = cam.shape[0]
+    res = torch.empty(E, dtype=torch.float32, device=cam.device) if out is None else out
+    _dev_check(what, ("out", res, torch.float32))
+    if d.shape != (E,) or res.shape != (E,):
+        raise ValueError(f"{what}: d and out must have one entry per edge")
+    check(lib().gasfm_depth_rescale(_p(d), _p(cam), _p(pt), is64, E, _p(M), M.stride(0), m, n, _p(Ns), _p(R), _p(res),
+                                    _stream(cam)), "gasfm_depth_rescale")
+    return res
 
 
 def sum_n(tensors):

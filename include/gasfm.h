@@ -1141,6 +1141,37 @@ int gasfm_scene_shard_point_csr(const int32_t* pt_ptr, const int32_t* perm, cons
                                 int64_t E_loc, int32_t* lpt_ptr, int64_t* cam_per_pts, uint8_t* valid_pt,
                                 int32_t* lperm, int32_t* lpos, void* stream);
 
+/* ---- Per-edge depth targets of a device scene (depth_targets.hip) ----
+ * The targets of the depth head (SceneData.depths, datasets/SceneData.py:57-134, a dense [m, n] matrix
+ * in the reference) as d [E] float32 in the scene's camera-major edge order; cam / pt per edge are
+ * int32 or int64 as the *_is64 flag says.  Grid-stride kernels without LDS, float atomics or any
+ * order-dependent sum: deterministic.  E = 0 returns GASFM_OK before any pointer is touched.  An edge
+ * whose index lies outside its array is not followed: its output is NaN and it is counted.
+ * `part`: gasfm_depth_part_slots(E) int32 of scratch for the per-wave counts. */
+int64_t gasfm_depth_part_slots(int64_t E);
+
+/* d[e] = a[cam[e]] . X[pt[e]] with a [m x 4] (the third row of Ns[c] @ y[c]) and X [n x 4]
+ * (homogeneous, last coordinate 1), both 16-byte aligned; bad[0] = the number of edges whose depth
+ * is not finite or not > 0 (the reference's asserts, SceneData.py:104 and :132). */
+int gasfm_depth_targets(const float* a, int32_t m, const float* X, int32_t n, const void* cam, const void* pt,
+                        int32_t idx_is64, int64_t E, float* d, int32_t* part, int32_t* bad, void* stream);
+
+/* SceneData.sample_data (:318-350) per edge: d[e] = pd[j], j the parent's edge of camera
+ * view_idx[cam[e]] and point keep[pt[e]], found by binary search over the ascending point ids ppt of
+ * the parent's camera row [pcam_ptr[c], pcam_ptr[c + 1]) (pcam_ptr [mp + 1], ppt / pd [Ep]; view_idx
+ * [ms], keep [ns] int64).  missing[0] = the number of edges without a parent edge (NaN in d). */
+int gasfm_depth_gather(const int32_t* pcam_ptr, const void* ppt, int32_t ppt_is64, const float* pd, int32_t mp,
+                       int64_t Ep, const int64_t* view_idx, const int64_t* keep, int32_t ms, int32_t ns,
+                       const void* cam, const void* pt, int32_t idx_is64, int64_t E, float* d, int32_t* part,
+                       int32_t* missing, void* stream);
+
+/* SceneData.apply_rotational_homography_aug (:434) per edge: out[e] = d[e] / z_old * z_new in fp32
+ * (divide, then multiply), q = Ns[c] @ (u, v, 1), z_old = q[2], z_new = (R[c] @ q)[2], (u, v) =
+ * (M[2c, p], M[2c + 1, p]) of the un-augmented dense M [2m x n] (row stride ldM); Ns, R [m x 3 x 3]. */
+int gasfm_depth_rescale(const float* d, const void* cam, const void* pt, int32_t idx_is64, int64_t E, const float* M,
+                        int64_t ldM, int32_t m, int32_t n, const float* Ns, const float* R, float* out,
+                        void* stream);
+
 /* dst[i] = src[0][i] + ... + src[n-1][i] (index order), n <= 16, count % 4 == 0, 16-byte aligned
  * rows: the gradient of a tensor with n consumers in one pass (the embedded projection input P0
  * feeds every block's projection update, layers.py:245-251; autograd would add n-1 times). */
