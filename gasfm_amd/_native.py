@@ -4,6 +4,11 @@ The HIP library is REQUIRED: if ``libgasfm.so`` is missing or fails to load,
 importing the compute entry points raises — there is no CPU or PyTorch
 fallback for the attention path.  Host-only entry points (graph
 preprocessing) work without a GPU, so DataLoader workers can use them.
+
+Nothing here restates the header: every signature, struct layout and constant
+comes from ``_abi``, which parses include/gasfm.h at import.  A new entry point
+is declared in gasfm.h, defined in csrc/ and wrapped here; there is no table to
+extend.
 """
 import ctypes
 import threading
@@ -12,221 +17,18 @@ import os
 import numpy as np
 import torch
 
+from . import _abi
 from .build import LIB
 
-GASFM_OK, GASFM_ERR_INVALID, GASFM_ERR_OOM, GASFM_ERR_HIP, GASFM_ERR_UNSUPPORTED = range(5)
+_C = _abi.constants
+GASFM_OK, GASFM_ERR_INVALID, GASFM_ERR_OOM, GASFM_ERR_HIP, GASFM_ERR_UNSUPPORTED = (
+    _C[k] for k in ("GASFM_OK", "GASFM_ERR_INVALID", "GASFM_ERR_OOM", "GASFM_ERR_HIP", "GASFM_ERR_UNSUPPORTED"))
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
 _i64 = ctypes.c_int64
-_f32 = ctypes.c_float
 
-# name -> (restype, argtypes); mirrors include/gasfm.h
-_SIGS = {
-    "gasfm_last_error": (ctypes.c_char_p, []),
-    "gasfm_version": (_i32, []),
-    "gasfm_dispatch_counts": (_i32, [_vp, _i32]),
-    "gasfm_dispatch_reset": (None, []),
-    "gasfm_tuning_set": (_i32, [_i32, ctypes.c_double]),
-    "gasfm_tuning_get": (ctypes.c_double, [_i32]),
-    "gasfm_build_csr": (_i32, [_vp, _i64, _i32, _vp, _vp]),
-    "gasfm_plan_work": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_gat_attn_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32,
-                                  _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
-    "gasfm_gat_attn_combine": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
-    "gasfm_gat_attn_bwd_waves": (_i32, [_i32, _i32, _i32]),
-    "gasfm_gat_attn_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp,
-                                  _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp]),
-    "gasfm_gat_attn_bwd_lanes": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp,
-                                  _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp]),
-    "gasfm_gat_attn_fwd_lanes": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32,
-                                  _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
-    "gasfm_gat_attn_bwd_combine": (_i32, [_vp, _i32, _i32, _vp, _vp, _i64, _vp]),
-    "gasfm_gat_attn_bwd_combine2": (_i32, [_vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
-    "gasfm_colsum_ws_floats": (_i64, [_i64, _i32]),
-    "gasfm_edge_part_floats": (_i32, [_i32, _i64, _i32]),
-    "gasfm_edge_prologue_fwd": (_i32, [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
-    "gasfm_edge_epilogue_fwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _i32, _vp, _vp, _vp, _i64,
-                                       _vp, _f32, _vp, _vp]),
-    "gasfm_edge_epilogue_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _f32, _vp, _vp, _vp,
-                                       _vp, _vp]),
-    "gasfm_edge_seam_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _f32, _vp, _vp,
-                                   _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _i32,
-                                   _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
-    "gasfm_edge_cam_pbwd_part_rows": (_i32, [_i32]),
-    "gasfm_edge_cam_pbwd_part_cols": (_i32, []),
-    "gasfm_edge_cam_pbwd": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _i64, _vp, _vp, _f32, _vp,
-                                   _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp,
-                                   _vp, _vp]),
-    "gasfm_edge0_seam_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32,
-                                    _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _f32,
-                                    _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
-    "gasfm_edge_cam_pbwd_ex": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _i64, _vp, _vp, _f32,
-                                      _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i64,
-                                      _vp, _vp, _i64, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _vp]),
-    "gasfm_edge_cam_fwd": (_i32, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _f32,
-                                  _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
-    "gasfm_edge_prologue_bwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _f32, _vp,
-                                       _vp, _vp, _i64, _vp]),
-    "gasfm_segment_rowsum": (_i32, [_vp, _i32, _vp, _vp, _i64, _f32, _vp, _vp, _vp]),
-    "gasfm_sos_width_ok": (_i32, [_i32, _i32]),
-    "gasfm_sos_row_tile": (_i32, [_i32]),
-    "gasfm_sos_segment_sum": (_i32, [_vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp]),
-    "gasfm_sos_edge_fwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp,
-                                  _vp]),
-    "gasfm_sos_edge_dx": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_sos_dw_splits": (_i32, [_i64, _i32, _i32]),
-    "gasfm_sos_edge_dw": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
-    "gasfm_colsum_counters": (_i32, [_i32]),
-    "gasfm_colsum_multi": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_colsum_multi_counters": (_i32, [_i32, _vp]),
-    "gasfm_colsum": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
-    "gasfm_colsum_tall_ok": (_i32, [_i32]),
-    "gasfm_colsum_tall_ws_floats": (_i64, [_i64, _i32]),
-    "gasfm_colsum_tall": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
-    "gasfm_colsum_ranges": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp]),
-    "gasfm_edge0_part_rows": (_i32, [_i32, _i64, _i32]),
-    "gasfm_edge0_prologue_fwd": (_i32, [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_edge0_prologue_fwd_rows": (_i32, [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_edge0_epilogue_fwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
-                                        _vp, _i64, _vp, _f32, _vp, _vp]),
-    "gasfm_edge0_epilogue_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _f32, _vp, _vp,
-                                        _vp, _vp, _vp]),
-    "gasfm_edge0_prologue_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp]),
-    "gasfm_node_part_rows": (_i32, [_i64, _i32, _i32]),
-    "gasfm_gvec_fwd": (_i32, [_vp, _i32, _vp, _vp, _f32, _vp, _vp, _i32, _vp, _vp, _vp]),
-    "gasfm_gvec_bwd_chunks": (_i32, [_i32]),
-    "gasfm_gvec_bwd": (_i32, [_vp, _vp, _i32, _vp, _vp, _f32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_node_ln_linear_fwd": (_i32, [_vp, _i64, _i32, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _vp, _i64, _vp]),
-    "gasfm_node_ln_linear_bwd": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _f32, _vp, _i32, _i32, _vp, _vp, _vp]),
-    "gasfm_view_tail_part_cols": (_i32, [_i32]),
-    "gasfm_view_hub_part_cols": (_i32, [_i32]),
-    "gasfm_view_scratch_floats": (_i64, [_i64, _i32]),
-    "gasfm_view_tail_fwd": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp,
-                                   _vp]),
-    "gasfm_view_tail_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_view_hub_fwd": (_i32, [_vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                  _vp, _i32, _vp, _vp, _vp]),
-    "gasfm_view_hub_bwd": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                  _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_gvec_multi_fwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp]),
-    "gasfm_gvec_multi_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
-                                    _vp, _vp, _f32, _vp]),
-    "gasfm_view_chain_ok": (_i32, [_i64, _i32]),
-    "gasfm_view_chain_scratch_floats": (_i64, [_i64, _i32]),
-    "gasfm_view_chain_counters": (_i32, [_i64]),
-    "gasfm_view_chain_tail_fwd": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp,
-                                         _vp]),
-    "gasfm_view_chain_hub_fwd": (_i32, [_vp, _i64, _i32, _f32] + [_vp] * 15 + [_i32, _vp, _vp]),
-    "gasfm_view_chain_hub_bwd": (_i32, [_vp, _vp, _i64, _i32] + [_vp] * 18),
-    "gasfm_view_chain_tail_bwd": (_i32, [_vp] * 5 + [_i64, _i32] + [_vp] * 12),
-    "gasfm_gchain_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_gchain_scratch_floats": (_i64, [_vp]),
-    "gasfm_gchain_counters": (_i32, [_vp]),
-    "gasfm_gchain_bwd": (_i32, [_vp] * 16),
-    "gasfm_gatt_scratch_floats": (_i64, [_i32, _vp]),
-    "gasfm_gatt_counters": (_i32, [_i32, _vp]),
-    "gasfm_gatt_fwd": (_i32, [_i32, _vp, _f32, _vp, _vp, _vp]),
-    "gasfm_gatt_bwd": (_i32, [_i32, _vp, _f32, _vp, _vp, _vp]),
-    "gasfm_gatt_merge": (_i32, [_i32, _vp, _i32, _i64, _vp]),
-    "gasfm_exchange_unpack": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp]),
-    "gasfm_gatt_merge_unpack": (_i32, [_i32, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i64,
-                                       _vp]),
-    "gasfm_pose_fwd": (_i32, [_vp, _i64, _i64, _vp, _vp]),
-    "gasfm_pose_bwd": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _vp]),
-    "gasfm_esfm_part_rows": (_i32, [_i64]),
-    "gasfm_reproj_error": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "gasfm_scene_mask_words": (_i64, [_i32]),
-    "gasfm_scene_tiles": (_i64, [_i32, _i32]),
-    "gasfm_scan_i32": (_i32, [_vp, _i64, _vp, _vp]),
-    "gasfm_scene_mask": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_scene_emit": (_i32, [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_scene_point_csr": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
-    "gasfm_scene_homography": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "gasfm_scene_shard_bounds": (_i32, [_vp, _i32, _i32, _vp, _vp]),
-    "gasfm_scene_shard_cam_range": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_scene_shard_stats": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
-    "gasfm_scene_shard_emit": (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                      _vp, _vp, _vp]),
-    "gasfm_scene_shard_point_csr": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
-                                           _vp]),
-    "gasfm_depth_part_slots": (_i64, [_i64]),
-    "gasfm_depth_targets": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
-    "gasfm_depth_gather": (_i32, [_vp, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i64, _vp,
-                                  _vp, _vp, _vp]),
-    "gasfm_depth_rescale": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
-    "gasfm_outlier_counts": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
-    "gasfm_outlier_mark": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
-    "gasfm_outlier_moments": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_outlier_apply": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
-    "gasfm_ba_partials": (_i64, [_i64]),
-    "gasfm_ba_eval": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
-                             _vp]),
-    "gasfm_ba_sum": (_i32, [_vp, _i64, _vp, _vp]),
-    "gasfm_ba_normals": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_ba_damp": (_i32, [_i32, _i32, _i32, _vp, _vp, ctypes.c_double, _vp, _vp, _vp, _vp]),
-    "gasfm_ba_schur": (_i32, [_i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
-                              _vp, _vp, _vp, _vp]),
-    "gasfm_ba_backsub": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_ba_model": (_i32, [_i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_ba_dlt": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_sum_n": (_i32, [_i32, _vp, _i64, _vp, _vp]),
-    "gasfm_esfm_fwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp]),
-    "gasfm_esfm_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _f32, _f32, _i32, _i32,
-                              _i32, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_esfm_seg_part_rows": (_i32, [_i32]),
-    "gasfm_esfm_seg_fwd": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp, _vp,
-                                  _vp]),
-    "gasfm_esfm_seg_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _f32,
-                                  _f32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_ose_part_rows": (_i32, [_i64]),
-    "gasfm_ose_fwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _f32, _vp, _vp]),
-    "gasfm_ose_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
-    "gasfm_ose_seg_part_rows": (_i32, [_i32]),
-    "gasfm_ose_seg_fwd": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
-    "gasfm_ose_seg_bwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _f32,
-                                 _vp, _vp, _vp, _vp]),
-    "gasfm_depth_loss_part_rows": (_i32, [_i64]),
-    "gasfm_depth_loss_sums": (_i32, [_vp, _vp, _i64, _vp, _vp]),
-    "gasfm_depth_loss_fwd": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp]),
-    "gasfm_depth_loss_bwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
-    "gasfm_reproj_error_seg": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "gasfm_depth_stats_ws_doubles": (_i64, [_i64]),
-    "gasfm_depth_stats": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
-                                 _vp]),
-    "gasfm_union_fill_scene": (_i32, [_vp, _vp, _vp]),
-    "gasfm_fold_scene_rows_fwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp]),
-    "gasfm_fold_scene_rows_bwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
-    "gasfm_adam_step": (_i32, [_vp, _vp, _i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                               ctypes.c_double, _i64, _vp]),
-    "gasfm_grad_sumsq": (_i32, [_vp, _vp, _i32, _vp, _vp]),
-    "gasfm_grad_sumsq_finish": (_i32, [_vp, _i64, _vp, _vp, _vp]),
-    "gasfm_grad_clip": (_i32, [_vp, _vp, _i32, _i32, ctypes.c_double, _vp, _vp]),
-    "gasfm_adam_control": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_double, _vp, ctypes.c_double, ctypes.c_double, _i32,
-                                  ctypes.c_double, _vp]),
-    "gasfm_adam_step_ctl": (_i32, [_vp, _vp, _i32, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                   ctypes.c_double, _i32, ctypes.c_double, _vp]),
-    "gasfm_union_fill_pad": (_i32, [_vp, _vp, _vp]),
-    "gasfm_sos_union_tables": (_i32, [_vp, _vp]),
-    "gasfm_point_tail_part_shape": (_i32, [_i64, _i32, _vp]),
-    "gasfm_point_hub_part_shape": (_i32, [_i64, _i32, _i32, _vp]),
-    "gasfm_point_tail_fwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp]),
-    "gasfm_point_tail_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_point_hub_fwd": (_i32, [_vp, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                   _vp, _vp, _vp]),
-    "gasfm_point_tail_hub_fwd": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _f32] + [_vp] * 15),
-    "gasfm_point_hub_bwd": (_i32, [_vp, _i64, _f32] + [_vp] * 17),
-    "gasfm_point_head_part_shape": (_i32, [_i64, _i32, _vp]),
-    "gasfm_point_head_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_point_head_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "gasfm_embed2_part_rows": (_i32, [_i64]),
-    "gasfm_embed2_fwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp]),
-    "gasfm_embed2_bwd": (_i32, [_vp, _vp, _i64, _vp, _vp]),
-    "gasfm_gemm_bf16": (_i32, [_i32, _i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
-    "gasfm_gemm_f32": (_i32, [_i32, _i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
-    "gasfm_gemm_f32_smallm_ok": (_i32, [_i32, _i32, _i32, _i32]),
-    "gasfm_gemm_f32_smallm": (_i32, [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
-}
+_SIGS = _abi.functions  # name -> (restype, argtypes)
 
 _lib = None
 
@@ -278,19 +80,18 @@ def _stream(t):
 
 
 # ---------------------------------------------------------------- kernel-choice record, tuning
-# mirrors the GASFM_K_* / GASFM_TUNE_* enums of include/gasfm.h
-KERNELS = {
-    "attn_fwd_grp": 0, "attn_fwd_glds": 1, "attn_fwd_vec": 2, "attn_fwd_generic": 3, "attn_fwd_lanes": 4,
-    "attn_bwd_glds": 5, "attn_bwd_vec": 6, "attn_bwd_generic": 7, "attn_bwd_lanes": 8,
-    "attn_combine_vec": 9, "attn_combine_generic": 10, "seam_reg": 13, "attn_fwd_grp_s2": 14, "attn_fwd_grp_s4": 15,
-    "sos_segsum": 16, "sos_edge_fwd": 17, "sos_edge_dx": 18, "sos_edge_dw": 19,
-}
-TUNING = {"attn_grp_rows": 0, "attn_grp_min_fill": 1, "attn_glds": 2, "attn_wave_cap": 3, "attn_grp_split": 4}
+def _enum(prefix):
+    """{lower-cased member name without the prefix: value} of an enum of gasfm.h, its _COUNT aside."""
+    return {k[len(prefix):].lower(): v for k, v in _C.items() if k.startswith(prefix) and k != prefix + "COUNT"}
+
+
+KERNELS = _enum("GASFM_K_")  # "attn_fwd_grp": 0, ... "sos_edge_dw": 19
+TUNING = _enum("GASFM_TUNE_")  # "attn_grp_rows": 0, ... "attn_grp_split": 4
 
 
 def dispatch_counts():
     """{kernel name: launches since the last reset} of the size-dependent dispatches."""
-    n = len(KERNELS) + 8
+    n = _C["GASFM_K_COUNT"]
     buf = (_i64 * n)()
     lib().gasfm_dispatch_counts(buf, n)
     return {k: int(buf[i]) for k, i in KERNELS.items()}
@@ -1438,20 +1239,9 @@ def depth_loss_bwd(a, b, sums, tot, l2, dloss):
     return da
 
 
-class UnionScene(ctypes.Structure):
-    _fields_ = ([("idx", _vp), ("ld_idx", _i64)] + [(k, _vp) for k in (
-        "vals", "vals_loss", "cptr", "pptr", "perm", "pos", "cam_per_pts", "pts_per_cam", "M")] + [("ldM", _i64),
-        ("Ns", _vp)] + [(k, _i64) for k in ("E", "m", "n", "e0", "c0", "p0", "item0")] + [("scene", _i32)])
-
-
-class UnionOut(ctypes.Structure):
-    _fields_ = ([("indices", _vp), ("ld_indices", _i64)] + [(k, _vp) for k in (
-        "cam32", "pt32", "values", "values_loss", "xy", "perm", "pos", "cam_ptr", "pt_ptr", "cam_per_pts",
-        "pts_per_cam", "soc", "soc32", "sop32", "Ns_inv", "items_c", "comb_c", "items_p")] + [("piece", _i32)])
-
-
-class UnionPad(ctypes.Structure):
-    _fields_ = [(k, _i64) for k in ("M", "N", "E", "mp", "npd", "ep", "dI", "item0")] + [("scene", _i32)]
+UnionScene = _abi.structs["gasfm_union_scene"]
+UnionOut = _abi.structs["gasfm_union_out"]
+UnionPad = _abi.structs["gasfm_union_pad"]
 
 
 def union_fill_scene(sc, out, stream_of):
@@ -1475,7 +1265,7 @@ def fold_scene_rows_bwd(dout, soc, S):
     return dsg
 
 
-ADAM_CHUNK = 4096  # GASFM_ADAM_CHUNK
+ADAM_CHUNK = _C["GASFM_ADAM_CHUNK"]
 
 
 def adam_step(tensors, chunks, n_chunks, lr, beta1, beta2, eps, weight_decay, step, stream_of):
@@ -1484,8 +1274,9 @@ def adam_step(tensors, chunks, n_chunks, lr, beta1, beta2, eps, weight_decay, st
                                 float(eps), float(weight_decay), int(step), _stream(stream_of)), "gasfm_adam_step")
 
 
-CLIP_MODES = {None: 0, "norm": 1, "value": 2}  # GASFM_CLIP_*
-ADAM_CTL_FLOATS = 8  # sizeof(gasfm_adam_ctl) / 4: int32 skip, then grad_norm, gscale, step_size, inv_bc2_sqrt
+CLIP_MODES = {None: _C["GASFM_CLIP_NONE"], "norm": _C["GASFM_CLIP_NORM"], "value": _C["GASFM_CLIP_VALUE"]}
+# a gasfm_adam_ctl as fp32 words: int32 skip, then grad_norm, gscale, step_size, inv_bc2_sqrt
+ADAM_CTL_FLOATS = ctypes.sizeof(_abi.structs["gasfm_adam_ctl"]) // 4
 
 
 def grad_sumsq(tensors, chunks, n_chunks, partial, stream_of):
@@ -1531,9 +1322,7 @@ _SOS_TABLES_F64 = ("Es", "degc", "invc", "wc", "degp", "invp", "wp")
 _SOS_TABLES_I64 = ("sop", "soe")
 
 
-class SosTables(ctypes.Structure):
-    _fields_ = ([(k, _vp) for k in _SOS_TABLES_IN] + [(k, _i64) for k in ("M", "N", "E")] + [("S", _i32)]
-                + [(k, _vp) for k in _SOS_TABLES_I32 + _SOS_TABLES_F64 + _SOS_TABLES_I64])
+SosTables = _abi.structs["gasfm_sos_tables"]
 
 
 def sos_tables_args(cam_ptr, pt_ptr, soc32, sop32, cam32, eoff, out):
@@ -1600,7 +1389,6 @@ def gvec_multi_bwd(probs, groups, eps):
 
 
 # ---------------------------------------------------------------- the global node's chain (global_chain.hip)
-_GC_DIMS = ("G", "Kc", "NA", "NB", "NC", "ND", "NE")
 _GC_W = ("W1", "b1", "gM", "bM", "W2", "b2", "gA", "bA", "WA", "gB", "bB", "WB", "bWB", "gC", "bC", "WC", "bWC",
          "WD", "bD", "WE", "bE")
 _GC_D = tuple("d" + k for k in _GC_W)
@@ -1609,16 +1397,9 @@ _GC_D = tuple("d" + k for k in _GC_W)
 _GC_SHADOW = ("W1", "W2", "WA", "WB", "WC", "WD", "WE")  # the weights with an optional bf16 shadow
 
 
-class _GChain(ctypes.Structure):
-    _fields_ = ([(k, _i32) for k in _GC_DIMS] + [("eps_m", _f32), ("eps_h", _f32)] + [(k, _vp) for k in _GC_W]
-                + [(k + "h", _vp) for k in _GC_SHADOW] + [("rows", _i32)])
-
-
-GCHAIN_MAX_ROWS = 7  # GASFM_GCHAIN_MAX_ROWS
-
-
-class _GChainGrads(ctypes.Structure):
-    _fields_ = [(k, _vp) for k in _GC_D]
+_GChain = _abi.structs["gasfm_gchain"]
+_GChainGrads = _abi.structs["gasfm_gchain_grads"]
+GCHAIN_MAX_ROWS = _C["GASFM_GCHAIN_MAX_ROWS"]
 
 
 def gchain_struct(w, eps_m, eps_h, shadows=None, rows=1):
@@ -1672,10 +1453,7 @@ def gchain_bwd(c, xcat, x1, g, xv, xp, dskip, dsg, dxrv, dxrp, dxcat, dprev, gra
 
 
 # ---------------------------------------------------------------- global GATv2 convs (global_attn.hip)
-class _GattProb(ctypes.Structure):
-    _fields_ = [("XL", _vp), ("ldXL", _i64), ("src", _vp), ("S", _i32), ("HC", _i32), ("XR", _vp), ("att", _vp),
-                ("bias", _vp), ("out", _vp), ("smax", _vp), ("ssum", _vp), ("part", _vp), ("gout", _vp),
-                ("dXL", _vp), ("ldDXL", _i64), ("dXR", _vp), ("datt", _vp)]
+_GattProb = _abi.structs["gasfm_gatt_prob"]
 
 
 def _gatt_probs(probs):

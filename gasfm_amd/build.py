@@ -13,6 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgasfm.so")
+HEADER = os.path.join(HERE, "..", "include", "gasfm.h")  # the C ABI; gasfm_amd/_abi.py reads the binding from it
 ARCH = os.environ.get("GASFM_OFFLOAD_ARCH", "gfx950")
 
 
@@ -33,8 +34,7 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.hpp")) + [
-        os.path.join(HERE, "..", "include", "gasfm.h")]
+    deps = sources() + glob.glob(os.path.join(CSRC, "*.hpp")) + [HEADER]
     return any(os.path.getmtime(p) > t for p in deps if os.path.exists(p))
 
 
