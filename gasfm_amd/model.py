@@ -27,6 +27,7 @@ import torch.nn.functional as F
 from torch.nn import Identity, LayerNorm, Linear, Module, ModuleList, ReLU, Sequential
 
 from . import _native, dense, edge_block, edge_ops, point_block, view_block
+from . import depth_head as depth_head_op
 from .attention import AttnPlan, GatAttentionFn, gat_attention
 from .edge_block import (Block0PrologueFn, CamArgs, DualAttentionFn, EdgeCamFn, EdgePrologueFn, Epilogue0Args,
                          EpilogueArgs, PendingEpilogue, materialize)
@@ -1171,8 +1172,10 @@ class GraphAttnSfMNet(BaseNet):
         if self.depth_head_enabled:
             from .scene import SparseMat
             x = data.x
-            pred["depths"] = SparseMat(self.depth_head(P), x.indices, x.cam_per_pts, x.pts_per_cam,
-                                       [x.shape[0], x.shape[1], 1])
+            # the fused 128-128-128-1 head (csrc/depth_head.hip) where it applies, else the Sequential as is
+            d = depth_head_op.apply(self.depth_head, P) if depth_head_op.fusable(self.depth_head, P) \
+                else self.depth_head(P)
+            pred["depths"] = SparseMat(d, x.indices, x.cam_per_pts, x.pts_per_cam, [x.shape[0], x.shape[1], 1])
         if self.view_head_enabled:
             out = self.extract_view_outputs(dense.sequential(self.view_head, F.relu(view)))
             shard = edges.plans.get("_shard")

@@ -33,6 +33,7 @@ import torch.nn.functional as F
 from torch.nn import Linear, Module, ModuleList
 
 from . import _native, dense
+from . import depth_head as depth_head_op
 from .model import BaseNet, EmbeddingLayer, ProjLayer, get_linear_layers, scene_edge_index
 
 
@@ -469,8 +470,9 @@ class SetOfSetNet(BaseNet):
         if self.depth_head_enabled:
             from .scene import SparseMat
             sx = data.x
-            pred["depths"] = SparseMat(self.depth_head(x), sx.indices, sx.cam_per_pts, sx.pts_per_cam,
-                                       [sx.shape[0], sx.shape[1], 1])
+            d = depth_head_op.apply(self.depth_head, x) if depth_head_op.fusable(self.depth_head, x) \
+                else self.depth_head(x)
+            pred["depths"] = SparseMat(d, sx.indices, sx.cam_per_pts, sx.pts_per_cam, [sx.shape[0], sx.shape[1], 1])
         if self.view_head_enabled or self.scenepoint_head_enabled:
             if self.composite:
                 mp, mc, _ = _composite_means(x, edges)
