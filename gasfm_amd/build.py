@@ -15,6 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgasfm.so")
 HEADER = os.path.join(HERE, "..", "include", "gasfm.h")  # the C ABI; gasfm_amd/_abi.py reads the binding from it
 DEPTH_HEAD_HEADER = os.path.join(HERE, "..", "include", "gasfm_depth_head.h")  # read by gasfm_amd/depth_head/_binding.py
+DEPTH_EVAL_HEADER = os.path.join(HERE, "..", "include", "gasfm_depth_eval.h")  # read by gasfm_amd/depth_eval/_binding.py
 ARCH = os.environ.get("GASFM_OFFLOAD_ARCH", "gfx950")
 
 
@@ -35,7 +36,7 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.hpp")) + [HEADER, DEPTH_HEAD_HEADER]
+    deps = sources() + glob.glob(os.path.join(CSRC, "*.hpp")) + [HEADER, DEPTH_HEAD_HEADER, DEPTH_EVAL_HEADER]
     return any(os.path.getmtime(p) > t for p in deps if os.path.exists(p))
 
 

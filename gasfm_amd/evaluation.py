@@ -10,12 +10,19 @@ here only the E observed (camera, point) pairs are projected, by ``gasfm_reproj_
   our_repro = nanmean_e || xy_e - pi(Ns_c^-1 Ps_norm_c pflat(pts3D)_p) ||   (pixels)
 
 The visible set is ``get_M_valid_points(xs)`` -- exactly the network's edges (data.x.indices).
-The depth-head branch (``eval.calc_reprojerr_with_gtposes_for_depth_pred``) needs a depth head,
-which every GASFM configuration disables; it raises like the reference does without one.
+The depth-head branch (``eval.calc_reprojerr_with_gtposes_for_depth_pred``) adds
+``repro_backproj_rnd_gt_2view``: every edge's pixel is backprojected with its predicted depth
+(rescaled by s_gt / s_pred, the mean depths) and reprojected at another edge of the same track with
+the ground-truth cameras -- gasfm_depth_norm_stats, gasfm_track_cycle and gasfm_backproj_2view
+(csrc/depth_eval.hip, gasfm_amd/depth_eval) in place of the reference's dense [m, n, 3] fp64 arrays.
+The random pairing is drawn on the device (torch.manual_seed governs it); ``pairing=`` takes a
+ready src [E] instead.  Without a depth head or a calibrated scene it raises like the reference.
 
 Scene evaluation (train.epoch_evaluation, reference train.py:170-259) runs on the same edges:
 ``prepare_predictions`` / ``compute_errors`` / ``get_dummy_errors`` keep the reference's signatures
-and dict keys (code/evaluation.py:76-432) for the GASFM configurations (both heads enabled).
+and dict keys (code/evaluation.py:76-432), for the explicit heads, the depth head, or both.  The
+depth head adds ``depth_{pred,gt}_norm_*``, ``depth_pred_err_mean`` and, with the flag above,
+``repro_backproj_*_rnd_gt_2view``; quantiles are one device sort per array (np.quantile's linear rule).
 
   triangulation      gasfm_ba_dlt through ba._Edges built from the scene's own edges
   repro errors       gasfm_reproj_error (our_repro, triangulated_repro, repro_ba)
@@ -37,8 +44,8 @@ from time import time
 import numpy as np
 import torch
 
-from . import _native
-from .loss import _edge_tensors, scene_csr
+from . import _native, depth_eval
+from .loss import _edge_depth_targets, _edge_tensors, scene_csr
 
 
 def _pixel_measurements(data):
@@ -93,36 +100,129 @@ def reprojection_error_mean(data, pred_dict, per_edge=False):
     return (mean, err) if per_edge else mean
 
 
-def compute_core_errors(data, pred_dict, conf):
+# ------------------------------------------------------------------ depth head
+def _per_edge(t, E, name):
+    """[E] values of a SparseMat ([E, 1] values) or of a plain [E] / [E, 1] tensor, detached."""
+    v = t if torch.is_tensor(t) else t.values
+    v = v.detach()
+    if v.dim() == 2 and v.shape[1] == 1:
+        v = v[:, 0]
+    if v.dim() != 1 or v.shape[0] != E:
+        raise ValueError(f"{name}: expected {E} per-edge values, got {tuple(v.shape)}")
+    return v.contiguous()
+
+
+def _depth_pair(data, pred_dict):
+    """(predicted depths [E], target depths [E]) in the scene's edge order."""
+    dep = pred_dict["depths"]
+    idx = data.x.indices
+    dp = _per_edge(dep, idx.shape[1], "pred_dict['depths']")
+    tgt = getattr(data, "depths", None)
+    if tgt is not None and tgt.dim() == 1 and not tgt.is_cuda:  # per-edge targets of a CPU scene
+        return dp, _per_edge(tgt, idx.shape[1], "data.depths")
+    return dp, _edge_depth_targets(data, idx)
+
+
+def _camera_table(data, dtype, device):
+    """depth_eval.camera_table of the scene's ground-truth cameras, once per scene, device and dtype:
+    keyed on the storage and version of y and Ns, as _pixel_measurements keys pixel_xy.  Ks is
+    Ns_invT^T where the scene carries it (the reference's Ks), else Ns^-1 in fp64."""
+    if data.y is None:
+        raise ValueError("depth evaluation: the scene carries no ground-truth cameras y")
+    Ns_invT = getattr(data, "Ns_invT", None)
+    Ksrc = Ns_invT if Ns_invT is not None else data.Ns
+    if Ksrc is None:
+        raise ValueError("depth evaluation: the scene carries no normalisation matrices Ns")
+    caches = scene_csr(data)[0]
+    key = (data.y.data_ptr(), data.y._version, Ksrc.data_ptr(), Ksrc._version, str(device), dtype)
+    cached = caches.get("camtab")
+    if cached is None or cached[0] != key:
+        Ksrc = Ksrc.to(device)
+        K = Ksrc.transpose(1, 2) if Ns_invT is not None else torch.linalg.inv(Ksrc.double())
+        cached = (key, depth_eval.camera_table(K, data.y.to(device), dtype))
+        caches["camtab"] = cached
+    return cached[1]
+
+
+def _pairing(pairing, E, device):
+    src = torch.as_tensor(pairing).to(device=device, dtype=torch.int32).contiguous()
+    if src.dim() != 1 or src.shape[0] != E:
+        raise ValueError(f"pairing: expected src [{E}], got {tuple(src.shape)}")
+    return src
+
+
+def backproj_2view_error(data, dp, dg, pairing=None, per_edge=False):
+    """The 2-view error of per-edge depths dp, rescaled to the targets dg: scales -> keys -> pairing ->
+    2-view kernel -> colsum, nothing read on the host.  Returns (tot [2] = sum and count of the non-NaN
+    errors, scales [2] = s_pred, s_gt), with ``per_edge`` also (err [E], rdepth [E]).  ``pairing``:
+    a ready src [E] (checked to stay within the tracks) instead of a random draw."""
+    (cam, pt), _, _, pt_ptr, pt_perm = _edge_tensors(data)
+    dev = cam.device
+    xy = _pixel_measurements(data)
+    kernels = dp.is_cuda and dp.dtype == torch.float32
+    scales, _ = depth_eval.depth_norm_stats(dp, dg, stats=False)
+    scale = scales[1] / scales[0]  # predicted depths / s_pred * s_gt without a rescaled copy
+    if pairing is None:
+        src, _ = depth_eval.track_cycle(pt_ptr, pt_perm, depth_eval.draw_keys(cam.shape[0], dev))
+        check = None
+    else:
+        src, check = _pairing(pairing, cam.shape[0], dev), pt
+    tab = _camera_table(data, torch.float32 if kernels else torch.float64, dev)
+    res = depth_eval.backproj_2view(cam, check, xy, dp, scale, src, tab, per_edge)
+    return (res[0], scales) + tuple(res[1:]) if per_edge else (res, scales)
+
+
+def _depth_conf(conf):
+    """(depth head enabled, 2-view error wanted), with the reference's refusals (evaluation.py:33-49)."""
+    depth_head = conf.get_bool("model.depth_head.enabled", default=False)
+    two_view = conf.get_bool("eval.calc_reprojerr_with_gtposes_for_depth_pred", default=False)
+    if two_view:
+        if not conf.get_bool("dataset.calibrated"):
+            raise ValueError("calc_reprojerr_with_gtposes_for_depth_pred needs a calibrated dataset")
+        if not depth_head:
+            # the reference raises NotImplementedError with both explicit heads and asserts otherwise
+            raise NotImplementedError("calc_reprojerr_with_gtposes_for_depth_pred requires the depth head")
+    return depth_head, two_view
+
+
+def compute_core_errors(data, pred_dict, conf, pairing=None):
     core_errors = {}
     view_head_enabled = conf.get_bool("model.view_head.enabled", default=False)
     scenepoint_head_enabled = conf.get_bool("model.scenepoint_head.enabled", default=False)
+    _, two_view = _depth_conf(conf)
     if view_head_enabled and scenepoint_head_enabled:
         core_errors["our_repro"] = float(reprojection_error_mean(data, pred_dict))
-    if conf.get_bool("eval.calc_reprojerr_with_gtposes_for_depth_pred", default=False):
-        # evaluation.py:33-48: needs the depth head (disabled in every GASFM conf); the reference
-        # raises NotImplementedError for the explicit-heads case as well
-        raise NotImplementedError("calc_reprojerr_with_gtposes_for_depth_pred requires the depth head")
+    if two_view:
+        tot, _ = backproj_2view_error(data, *_depth_pair(data, pred_dict), pairing=pairing)
+        core_errors["repro_backproj_rnd_gt_2view"] = float(tot[0] / tot[1])  # count 0 -> nan (np.nanmean)
     return core_errors
 
 
 # ------------------------------------------------------------------ scene evaluation
 def _heads(conf):
-    """(calibrated, both heads enabled); the depth-head branches of the reference need a depth head,
-    which no GASFM configuration has."""
-    if conf.get_bool("model.depth_head.enabled", default=False) or conf.get_bool(
-            "eval.calc_reprojerr_with_gtposes_for_depth_pred", default=False):
-        raise NotImplementedError("evaluation with the depth head is not supported")
+    """(calibrated, both explicit heads enabled)."""
     explicit = conf.get_bool("model.view_head.enabled", default=False) and conf.get_bool(
         "model.scenepoint_head.enabled", default=False)
     return conf.get_bool("dataset.calibrated"), explicit
 
 
 class PredictionOutputs(dict):
-    """prepare_predictions' result: the reference's keys; ``xs`` ([m, n, 2], dense) is built from
-    the scene on first access."""
+    """prepare_predictions' result: the reference's keys; ``xs`` ([m, n, 2], dense) and the dense
+    [m, n] ``depths_pred_dense`` / ``depths_gt_dense`` are built from the scene on first access."""
+
+    def _dense_depths(self, key):
+        dev = dict.__getitem__(self, "_device")
+        if key == "depths_gt_dense" and dev.get("depths_gt_dense") is not None:
+            return dev["depths_gt_dense"].detach().cpu().numpy()  # the scene's own dense data.depths
+        per_edge = dev["depths_pred" if key == "depths_pred_dense" else "depths_gt"]
+        dense = np.zeros((dev["m"], dev["n"]), dtype=per_edge.cpu().numpy().dtype)  # to_dense(): 0 elsewhere
+        dense[dev["cam"].cpu().numpy(), dev["pt"].cpu().numpy()] = per_edge.cpu().numpy()
+        return dense
 
     def __missing__(self, key):
+        if key in ("depths_pred_dense", "depths_gt_dense") and "depths_pred" in dict.__getitem__(self, "_device"):
+            self[key] = self._dense_depths(key)
+            return self[key]
         if key != "xs":
             raise KeyError(key)
         dev = dict.__getitem__(self, "_device")
@@ -263,13 +363,11 @@ _BA_REPEAT_KEYS = ("repro_before", "repro_middle", "repro_middle_triangulated", 
 def prepare_predictions(data, pred_dict, conf, bundle_adjustment):
     from . import ba
     calibrated, explicit = _heads(conf)
+    depth_head, two_view = _depth_conf(conf)
     outputs = PredictionOutputs()
     outputs["scene_name"] = data.scene_name
-    Ps_norm_d, pts3D_d = pred_dict["Ps_norm"], pred_dict["pts3D"]
-    if not Ps_norm_d.is_cuda or not pts3D_d.is_cuda:
-        raise TypeError("prepare_predictions: predictions must be CUDA tensors (no CPU fallback)")
-    dev = pts3D_d.device
     (cam, pt), _, cam_ptr, pt_ptr, pt_perm = _edge_tensors(data)
+    dev = cam.device
     xy = _pixel_measurements(data)
     m, n = int(data.x.shape[0]), int(data.x.shape[1])
     M = getattr(data, "M", None)
@@ -285,9 +383,27 @@ def prepare_predictions(data, pred_dict, conf, bundle_adjustment):
     if calibrated:
         Ks = Ns_inv  # Ks for calibrated scenes, a normalisation matrix otherwise
         outputs["Ks"] = Ks
+    if depth_head:
+        # evaluation.py:99-126; the dense depths_pred_dense / depths_gt_dense are built on first access
+        dp, dg = _depth_pair(data, pred_dict)
+        state["depths_pred"], state["depths_gt"] = dp, dg
+        tgt = getattr(data, "depths", None)
+        state["depths_gt_dense"] = tgt if tgt is not None and tgt.dim() == 2 else None
+        scales, _ = depth_eval.depth_norm_stats(dp, dg, stats=False)
+        state["scales"] = scales
+        s = scales.cpu().numpy()
+        outputs["s_pred"], outputs["s_gt"] = s[0], s[1]
+        if two_view:
+            outputs["Ps_gt"] = data.y.detach().cpu().numpy()
+            state["camtab"] = _camera_table(data, torch.float32 if dp.is_cuda and dp.dtype == torch.float32
+                                            else torch.float64, dev)
     if not explicit:
         return outputs
 
+    Ps_norm_d, pts3D_d = pred_dict["Ps_norm"], pred_dict["pts3D"]
+    if not Ps_norm_d.is_cuda or not pts3D_d.is_cuda:
+        raise TypeError("prepare_predictions: predictions must be CUDA tensors (no CPU fallback)")
+    dev = pts3D_d.device
     P = _pixel_cameras(data, Ps_norm_d)  # [m, 12] float32, Ns^-1 Ps_norm
     X = pts3D_d.detach().float().contiguous()
     state["P"], state["X"] = P, X
@@ -354,12 +470,71 @@ def _nanmean_repro(state, P, X):
     return float(tot[0] / tot[1])  # count 0 -> nan, as np.nanmean of an all-NaN array
 
 
-def compute_errors(outputs, conf, bundle_adjustment):
+_QUANTILES = (10, 25, 50, 75, 90)
+
+
+def _quantiles(x):
+    """np.quantile(x, 0.01 * [10, 25, 50, 75, 90]) (the default linear rule) of a per-edge device
+    vector as a [5] float64 device tensor: one sort, then the two neighbours of h = (E - 1) q
+    interpolated in fp64 the way numpy's lerp does.  A NaN anywhere gives NaN, as in numpy."""
+    E = x.shape[0]
+    if E == 0:
+        return torch.full((5,), float("nan"), dtype=torch.float64, device=x.device)
+    s = torch.sort(x).values  # NaN sorts last
+    h = (E - 1) * (0.01 * np.array(_QUANTILES))
+    lo = np.floor(h).astype(np.int64)
+    t = torch.as_tensor(h - lo, dtype=torch.float64, device=x.device)
+    a = s[torch.as_tensor(lo, device=x.device)].double()
+    b = s[torch.as_tensor(np.minimum(lo + 1, E - 1), device=x.device)].double()
+    q = torch.where(t >= 0.5, b - (b - a) * (1 - t), a + (b - a) * t)
+    return torch.where(torch.isnan(s[-1]), torch.full_like(q, float("nan")), q)
+
+
+def _norm_keys(prefix, suffix=""):
+    return ([f"{prefix}_mean{suffix}"] + [f"{prefix}_q{q:02d}{suffix}" for q in _QUANTILES]
+            + [f"{prefix}_min{suffix}", f"{prefix}_max{suffix}"])
+
+
+def _depth_errors(state, two_view, pairing):
+    """The depth head's keys of compute_errors (evaluation.py:241-301), in the reference's order;
+    every number is reduced on the device and read in one copy."""
+    dp, dg, scales = state["depths_pred"], state["depths_gt"], state["scales"]
+    E = dp.shape[0]
+    _, st = depth_eval.depth_norm_stats(dp, dg)
+    vals = [st[0] / E, _quantiles(dp / scales[0]), st[1:3], st[3:4] / E, _quantiles(dg / scales[1]), st[4:6],
+            st[6:7] / E]
+    keys = _norm_keys("depth_pred_norm") + _norm_keys("depth_gt_norm") + ["depth_pred_err_mean"]
+    if two_view:
+        cam, pt = state["cam"], state["pt"]
+        if pairing is None:
+            src, _ = depth_eval.track_cycle(state["pt_ptr"], state["perm"], depth_eval.draw_keys(E, cam.device))
+            check = None
+        else:
+            src, check = _pairing(pairing, E, cam.device), pt
+        tot, _, rdepth = depth_eval.backproj_2view(cam, check, state["xy"], dp, scales[1] / scales[0], src,
+                                                   state["camtab"], per_edge=True)
+        rn = rdepth / scales[1].to(rdepth.dtype)  # back to the normalised depth scale
+        vals += [tot[0:1].double() / tot[1:2].double(), rn.double().sum().view(1) / E if E else st[0:1],
+                 rn.min().view(1).double() if E else st[1:2], rn.max().view(1).double() if E else st[2:3],
+                 _quantiles(rn)]
+        sfx = "_rnd_gt_2view"
+        keys += ["repro_backproj" + sfx, "repro_backproj_depth_norm_mean" + sfx, "repro_backproj_depth_norm_min" + sfx,
+                 "repro_backproj_depth_norm_max" + sfx] + [f"repro_backproj_depth_norm_q{q:02d}{sfx}"
+                                                           for q in _QUANTILES]
+    host = torch.cat([v.reshape(-1).double() for v in vals]).cpu().numpy()
+    assert host.shape[0] == len(keys)
+    return dict(zip(keys, host))
+
+
+def compute_errors(outputs, conf, bundle_adjustment, pairing=None):
     calibrated, explicit = _heads(conf)
+    depth_head, two_view = _depth_conf(conf)
     model_errors = {}
+    state = outputs["_device"]
+    if depth_head:
+        model_errors.update(_depth_errors(state, two_view, pairing))
     if not explicit:
         return model_errors
-    state = outputs["_device"]
     model_errors["our_repro"] = _nanmean_repro(state, state["P"], state["X"])
     model_errors["triangulated_repro"] = _nanmean_repro(state, state["P"], state["X_tri"])
 
@@ -413,10 +588,20 @@ def get_dummy_errors(conf, bundle_adjustment):
     """The keys compute_errors would set, all NaN (after an out-of-memory scene).  Like the
     reference's (evaluation.py:368-432) it has no ba_time and no cam_centers*_std."""
     calibrated, explicit = _heads(conf)
+    keys = []
+    # the depth keys come first and in the reference's dummy order (mean, min, max, quantiles), which
+    # is not compute_errors' order; as there, each group follows its own conf key alone
+    def dummy_norm(prefix, sfx=""):
+        return [f"{prefix}_{k}{sfx}" for k in ("mean", "min", "max")] + [f"{prefix}_q{q:02d}{sfx}" for q in _QUANTILES]
+
+    if conf.get_bool("eval.calc_reprojerr_with_gtposes_for_depth_pred", default=False):
+        keys += ["repro_backproj_rnd_gt_2view"] + dummy_norm("repro_backproj_depth_norm", "_rnd_gt_2view")
+    if conf.get_bool("model.depth_head.enabled", default=False):
+        keys += dummy_norm("depth_pred_norm") + dummy_norm("depth_gt_norm") + ["depth_pred_err_mean"]
     if not explicit:
-        return {}
+        return {k: np.nan for k in keys}
     pose = ("t_err{}_mean", "t_err{}_med", "R_err{}_mean", "R_err{}_med")
-    keys = ["our_repro", "triangulated_repro"]
+    keys += ["our_repro", "triangulated_repro"]
     if calibrated:
         keys += [k.format("") for k in pose]
     if bundle_adjustment:
