@@ -16,6 +16,7 @@ LIB = os.path.join(HERE, "libgasfm.so")
 HEADER = os.path.join(HERE, "..", "include", "gasfm.h")  # the C ABI; gasfm_amd/_abi.py reads the binding from it
 DEPTH_HEAD_HEADER = os.path.join(HERE, "..", "include", "gasfm_depth_head.h")  # read by gasfm_amd/depth_head/_binding.py
 DEPTH_EVAL_HEADER = os.path.join(HERE, "..", "include", "gasfm_depth_eval.h")  # read by gasfm_amd/depth_eval/_binding.py
+DEPTH_BATCH_HEADER = os.path.join(HERE, "..", "include", "gasfm_depth_batch.h")  # read by gasfm_amd/depth_batch/_binding.py
 ARCH = os.environ.get("GASFM_OFFLOAD_ARCH", "gfx950")
 
 
@@ -36,7 +37,8 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.hpp")) + [HEADER, DEPTH_HEAD_HEADER, DEPTH_EVAL_HEADER]
+    deps = sources() + glob.glob(os.path.join(CSRC, "*.hpp")) + [HEADER, DEPTH_HEAD_HEADER, DEPTH_EVAL_HEADER,
+                                                                          DEPTH_BATCH_HEADER]
     return any(os.path.getmtime(p) > t for p in deps if os.path.exists(p))
 
 

@@ -16,6 +16,7 @@
 // on the host and every size follows from (E, m, n): two runs give the same bits and each entry can
 // be captured.
 #include "../../include/gasfm_depth_eval.h"
+#include "depth_edge.hpp"
 #include "edge_loss.hpp"
 
 namespace gasfm {
@@ -113,20 +114,7 @@ __global__ __launch_bounds__(kT) void track_single_kernel(const int32_t* __restr
 }
 
 // ---------------------------------------------------------------- 2-view error
-// camera row: [R | t] at 0, K^-1 at 12, K at 21 (GASFM_CAMTAB_FLOATS floats, 128 bytes)
-struct CamRow {
-  float4 q[8];
-  __device__ __forceinline__ float at(int i) const { return reinterpret_cast<const float*>(q)[i]; }
-};
-
-// float4s [first, first + count) of camera c's row
-template <int kFirst, int kCount>
-__device__ __forceinline__ void load_row(const float* __restrict__ tab, int c, CamRow& r) {
-  const float4* row = reinterpret_cast<const float4*>(tab + int64_t(c) * GASFM_CAMTAB_FLOATS);
-#pragma unroll
-  for (int i = kFirst; i < kFirst + kCount; ++i) r.q[i] = row[i];
-}
-
+// CamRow, load_row and the per-edge body backproj_edge: depth_edge.hpp (shared with depth_batch.hip)
 __global__ __launch_bounds__(kT) void backproj_2view_kernel(const int32_t* __restrict__ cam,
                                                             const int32_t* __restrict__ pt,
                                                             const float* __restrict__ xy,
@@ -139,39 +127,9 @@ __global__ __launch_bounds__(kT) void backproj_2view_kernel(const int32_t* __res
   __shared__ float sh[kW * 2];
   float acc[2] = {0.f, 0.f};
   const float s = E > 0 ? scale[0] : 0.f;
-  const float nan = __int_as_float(0x7fc00000);
   for (int64_t e2 = int64_t(blockIdx.x) * kT + threadIdx.x; e2 < E; e2 += int64_t(gridDim.x) * kT) {
-    float r = nan, z = nan;
-    const int32_t e = src[e2], c2 = cam[e2];
-    if (uint32_t(e) < uint64_t(E) && uint32_t(c2) < uint32_t(m)) {
-      const int32_t c = cam[e];
-      if (uint32_t(c) < uint32_t(m) && (!pt || pt[e] == pt[e2])) {
-        CamRow A, B;
-        load_row<0, 6>(tab, c, A);   // [R | t], K^-1 of the source camera
-        load_row<0, 3>(tab, c2, B);  // [R | t], K of the destination camera
-        load_row<5, 3>(tab, c2, B);
-        const float2 m1 = reinterpret_cast<const float2*>(xy)[e];
-        const float2 m2 = reinterpret_cast<const float2*>(xy)[e2];
-        float h[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) h[i] = fmaf(A.at(12 + 3 * i), m1.x, fmaf(A.at(13 + 3 * i), m1.y, A.at(14 + 3 * i)));
-        const float dd = s * d[e];
-        const float l[3] = {dd * (h[0] / h[2]) - A.at(3), dd * (h[1] / h[2]) - A.at(7), dd - A.at(11)};
-        float X[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) X[k] = fmaf(A.at(k), l[0], fmaf(A.at(4 + k), l[1], A.at(8 + k) * l[2]));
-        float q[3], y[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-          q[i] = fmaf(B.at(4 * i), X[0], fmaf(B.at(4 * i + 1), X[1], fmaf(B.at(4 * i + 2), X[2], B.at(4 * i + 3))));
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-          y[i] = fmaf(B.at(21 + 3 * i), q[0], fmaf(B.at(22 + 3 * i), q[1], B.at(23 + 3 * i) * q[2]));
-        const float u = m2.x - y[0] / y[2], v = m2.y - y[1] / y[2];
-        r = sqrtf(fmaf(u, u, v * v));
-        z = q[2];
-      }
-    }
+    float r, z;
+    backproj_edge(cam, pt, xy, d, s, src, E, tab, m, e2, r, z);
     if (err) err[e2] = r;
     if (rdepth) rdepth[e2] = z;
     const bool ok = !isnan(r);
@@ -202,23 +160,7 @@ __device__ __forceinline__ Stat stat_merge(const Stat& a, const Stat& b) {
                nan_min(a.v[4], b.v[4]), nan_max(a.v[5], b.v[5]), a.v[6] + b.v[6]}};
 }
 
-// tree over the thread index: a fixed order; the result is in every thread
-template <class T, class Merge>
-__device__ __forceinline__ T block_tree(T v, T* sh, Merge merge) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = kT / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) sh[threadIdx.x] = merge(sh[threadIdx.x], sh[threadIdx.x + s]);
-    __syncthreads();
-  }
-  return sh[0];
-}
-
-struct Sum2 {
-  double a, b;
-};
-
-__device__ __forceinline__ Sum2 sum2_merge(const Sum2& x, const Sum2& y) { return Sum2{x.a + y.a, x.b + y.b}; }
+// block_tree, Sum2 and sum2_merge: depth_edge.hpp
 
 // sums[row] = fp64 (sum dp, sum dg) of workgroup row's grid-stride slice
 __global__ __launch_bounds__(kT) void depth_sum_kernel(const float* __restrict__ dp, const float* __restrict__ dg,

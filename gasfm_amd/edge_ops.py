@@ -14,6 +14,11 @@ def layer_norm_relu(P, ln):
 
 
 def projection_update(x, lin_proj, sp, sv, sg, edges):
-    y = F.linear(x, lin_proj.weight, lin_proj.bias)
+    # dense.linear, not F.linear: on the device its bias gradient is the project's column sum.  aten's
+    # addmm backward takes torch's sum over the E rows, whose global reduction gives wrong sums when
+    # replayed from a captured hipGraph: a depth-head conf runs its last, 32 -> 128
+    # block through here inside StaticTrainer's captured step.
+    from . import dense
+    y = dense.linear(x, lin_proj)
     y = y + sp.index_select(0, edges.pt) + sv.index_select(0, edges.cam) + sg
     return y / 4

@@ -793,7 +793,7 @@ class GraphAttnSfMLayer(Module):
         if self.skip_projection is not None:
             if self.use_norm_proj_update:
                 skip = edge_ops.layer_norm_relu(skip, self.residual_skipconn_proj_norm_layer)
-            skip = self.skip_projection.lin_proj(skip)
+            skip = dense.linear(skip, self.skip_projection.lin_proj)  # as edge_ops.projection_update
         return skip + delta, pts, view, glob
 
 

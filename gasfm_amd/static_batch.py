@@ -51,7 +51,8 @@ from . import _native
 from .attention import DEFAULT_MAX_PIECE, AttnPlan
 from .batch import _scene_arrays
 from .graph_step import gc_paused
-from .loss import ESFMLoss, ExpDepthRegularizedOSELoss, _flat_inputs, _grad_buffers
+from .loss import (DirectDepthLoss, ESFMLoss, ExpDepthRegularizedOSELoss, _edge_depth_targets, _flat_inputs,
+                   _grad_buffers)
 from .model import EdgeIndex, require_gasfm
 from .scene import MIN_N_POINTS_PER_VIEW, MIN_N_VIEWS_PER_POINT, AxialAggregationGraphWrapper, SparseMat
 
@@ -279,6 +280,9 @@ class StaticBatch:
             (str(dev), self.indices.data_ptr()): EdgeIndex(self.cam32, self.pt32, M, N, plans)}
         self.offsets = None
         self._out = None
+        # the depth branch's static inputs, allocated by enable_depth()
+        self.depths = self.camtab = self.pair_keys = self.zero_err = self._xs = None
+        self.two_view_ready = False
         if dev.type == "cuda":
             o = _native.UnionOut()
             for k in ("indices", "cam32", "pt32", "values", "values_loss", "xy", "perm", "pos", "cam_ptr", "pt_ptr",
@@ -288,6 +292,49 @@ class StaticBatch:
             o.ld_indices = E
             o.piece = PIECE
             self._out = o
+
+    # ------------------------------------------------------------------ the depth branch's inputs
+    def enable_depth(self):
+        """Allocate the depth branch's static buffers (ESFM / OSE buckets never pay for them): per-edge
+        depth targets, the ground-truth camera table of the 2-view error and the pairing keys.  From
+        then on every fill writes the targets, and the cameras and fresh keys when its scenes carry
+        ``y``.  Defaults are the pad scene's: depth 1, identity [R | t] and K."""
+        if self.depths is None:
+            from .depth_eval import CAMTAB_FLOATS
+            c, dev = self.caps, self.device
+            self.depths = torch.ones(c.E, dtype=torch.float32, device=dev)
+            row = torch.zeros(CAMTAB_FLOATS, dtype=torch.float32, device=dev)
+            row[[0, 5, 10, 12, 16, 20, 21, 25, 29]] = 1.0  # [I | 0], K^-1 = K = I
+            self._camtab_pad = row
+            self.camtab = row.repeat(c.M, 1)
+            self.pair_keys = torch.zeros(c.E, dtype=torch.int32, device=dev)
+            self.zero_err = torch.zeros((c.S, 2), dtype=torch.float32, device=dev)
+        return self
+
+    def _fill_depth(self, datas, st, eo, mo):
+        """Per scene: data.depths (per-edge, or the dense form gathered once) and, where every scene
+        carries ground-truth cameras, its cached evaluation._camera_table rows; device copies.  The
+        pairing keys are drawn here, outside any captured graph, so a replay reads fresh keys."""
+        from . import depth_eval, evaluation
+        dev = self.device
+        for s, d in enumerate(datas):
+            if getattr(d, "depths", None) is None:
+                raise ValueError(f"StaticBatch.fill: scene '{getattr(d, 'scene_name', s)}' carries no depths")
+        self.two_view_ready = all(getattr(d, "y", None) is not None for d in datas)
+        for s, d in enumerate(datas):
+            dep = d.depths
+            if dep.dim() == 2 or dep.device != dev or dep.dtype != torch.float32:
+                dep = _edge_depth_targets(d, d.x.indices) if dep.dim() == 2 else dep.to(dev, torch.float32)
+            if dep.shape[0] != st.Es[s]:
+                raise ValueError(f"StaticBatch.fill: scene '{getattr(d, 'scene_name', s)}' has {dep.shape[0]} "
+                                 f"depths for {st.Es[s]} edges")
+            self.depths[eo[s]:eo[s + 1]].copy_(dep)
+            if self.two_view_ready:
+                self.camtab[mo[s]:mo[s + 1]].copy_(evaluation._camera_table(d, torch.float32, dev))
+        self.depths[st.E:].fill_(1.0)
+        self.camtab[st.M:].copy_(self._camtab_pad.expand(self.caps.M - st.M, -1))
+        self.pair_keys.copy_(depth_eval.draw_keys(self.caps.E, dev))
+        self._xs = [d.x for d in datas]
 
     @staticmethod
     def _pieces_np(seg, P):
@@ -416,6 +463,8 @@ class StaticBatch:
             self._global_plans_torch()
         if self._tables is not None:  # reads eoff: after the copy above, on the same stream
             _native.sos_union_tables(self._tables.args, self.values)
+        if self.depths is not None:
+            self._fill_depth(datas, st, eo, mo)
 
     def fill_torch(self, datas, st, inputs=None):
         """``fill`` in torch ops."""
@@ -518,6 +567,8 @@ class StaticBatch:
         self._global_plans_torch()
         if self._tables is not None:
             self._tables_torch()
+        if self.depths is not None:
+            self._fill_depth(datas, st, eo, mo)
 
     def _global_plans_torch(self):
         """view2global / scenepoint2global segments and items from the filled counts (torch ops)."""
@@ -550,9 +601,22 @@ class StaticBatch:
 
     def split(self, pred):
         """Per-scene prediction dicts (views into the union outputs) of the last fill."""
-        mo, no, _ = self.offsets
-        return [{"Ps_norm": pred["Ps_norm"][mo[i]:mo[i + 1]], "pts3D": pred["pts3D"][:, no[i]:no[i + 1]]}
-                for i in range(self.B)]
+        mo, no, eo = self.offsets
+        out = []
+        for i in range(self.B):
+            d = {}
+            if "Ps_norm" in pred:
+                d["Ps_norm"] = pred["Ps_norm"][mo[i]:mo[i + 1]]
+            if "pts3D" in pred:
+                d["pts3D"] = pred["pts3D"][:, no[i]:no[i + 1]]
+            if "depths" in pred:
+                if self._xs is None:
+                    raise ValueError("StaticBatch.split: depths need a fill after enable_depth()")
+                x = self._xs[i]
+                d["depths"] = SparseMat(pred["depths"].values[eo[i]:eo[i + 1]], x.indices, x.cam_per_pts,
+                                        x.pts_per_cam, [x.shape[0], x.shape[1], 1])
+            out.append(d)
+        return out
 
 
 class BatchLossFn(torch.autograd.Function):
@@ -585,8 +649,8 @@ def batch_loss(pred, sb, lossf):
     elif isinstance(lossf, ExpDepthRegularizedOSELoss):
         kernels = (_native.ose_seg_fwd, _native.ose_seg_bwd, (float(lossf.depth_regul_weight),), 1, False)
     else:
-        raise TypeError(f"batch_loss: no union-batch form of {type(lossf).__name__} (ESFMLoss and "
-                        "ExpDepthRegularizedOSELoss have one)")
+        raise TypeError(f"batch_loss: no Ps_norm / pts3D union-batch form of {type(lossf).__name__} (ESFMLoss and "
+                        "ExpDepthRegularizedOSELoss have one; DirectDepthLoss goes through batch_depth_loss)")
     return BatchLossFn.apply(pred["Ps_norm"], pred["pts3D"], sb, *kernels)
 
 
@@ -597,6 +661,62 @@ def batch_repro_errors(pred, sb):
     P = torch.bmm(sb.Ns_inv, Ps).reshape(-1, 12).contiguous()
     return _native.reproj_error_seg(sb.cam32, sb.pt32, sb.xy, sb.eoff, sb.caps.S, P,
                                     pred["pts3D"].detach().float().contiguous())
+
+
+class BatchDepthLossFn(torch.autograd.Function):
+    """a [E_cap] -> sum over the real scenes of DirectDepthLoss against sb.depths (depth_batch's
+    gasfm_depth_loss_seg_* kernels): the eager step's ``sum(lossf(p, d) for ...)`` with fixed launch geometry."""
+
+    @staticmethod
+    def forward(ctx, a, sb, l2):
+        from . import depth_batch
+        a = a.contiguous()
+        loss, sums, tot = depth_batch.depth_loss_seg_fwd(a, sb.depths, sb.eoff, sb.weight, l2)
+        ctx.save_for_backward(a, sums, tot)
+        ctx.sb, ctx.l2 = sb, l2
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        from . import depth_batch
+        a, sums, tot = ctx.saved_tensors
+        sb = ctx.sb
+        dloss = dloss.reshape(1).to(a.dtype).contiguous()
+        return depth_batch.depth_loss_seg_bwd(a, sb.depths, sb.eoff, sb.weight, sums, tot, ctx.l2, dloss), None, None
+
+
+def _union_depths(pred, sb):
+    dep = pred["depths"]
+    v = dep if torch.is_tensor(dep) else dep.values
+    if v.dim() == 2 and v.shape[1] == 1:
+        v = v[:, 0]
+    if v.dim() != 1 or v.shape[0] != sb.caps.E:
+        raise ValueError(f"expected {sb.caps.E} per-edge depths of the bucket, got {tuple(v.shape)}")
+    return v
+
+
+def batch_depth_loss(pred, sb, lossf):
+    """DirectDepthLoss of a depth-head model's ``pred["depths"]`` over a filled StaticBatch (after
+    ``sb.enable_depth()``): sum over the real scenes, the pad scene with weight 0."""
+    if not isinstance(lossf, DirectDepthLoss):
+        raise TypeError(f"batch_depth_loss: expected DirectDepthLoss, got {type(lossf).__name__}")
+    if sb.depths is None:
+        raise ValueError("batch_depth_loss: the bucket carries no depth targets (StaticBatch.enable_depth, then fill)")
+    return BatchDepthLossFn.apply(_union_depths(pred, sb), sb, lossf.cost_fcn == "L2")
+
+
+def batch_depth_errors(pred, sb):
+    """[S, 2] per-scene (sum, count) of the non-NaN 2-view errors (compute_core_errors'
+    repro_backproj_rnd_gt_2view = sum / count) of a StaticBatch, on the device: per-scene scales, the
+    pairing from sb.pair_keys (tracks do not cross scenes), then the segmented 2-view error."""
+    from . import depth_batch, depth_eval
+    if sb.depths is None or not sb.two_view_ready:
+        raise ValueError("batch_depth_errors: the bucket carries no ground-truth cameras (StaticBatch.enable_depth, "
+                         "then fill with scenes that have y)")
+    d = _union_depths(pred, sb).detach().contiguous()
+    scales = depth_batch.depth_scales_seg(d, sb.depths, sb.eoff)
+    src, _ = depth_eval.track_cycle(sb.pt_ptr, sb.perm, sb.pair_keys)
+    return depth_batch.backproj_2view_seg(sb.cam32, None, sb.xy, d, scales, src, sb.eoff, sb.camtab)
 
 
 class StaticTrainer:
@@ -616,12 +736,22 @@ class StaticTrainer:
 
     guard_loss: pass the bucket's static loss tensor to ``optimizer.step(loss=...)``, which then skips
     the update on the device unless the loss is > 0 (train.py:133; gasfm_amd.optim.Adam's device path).
-    ``grad_norm``: the optimizer's device-side gradient norm of the last step, or None."""
+    ``grad_norm``: the optimizer's device-side gradient norm of the last step, or None.
 
-    def __init__(self, net, lossf, warmup=2, optimizer=None, max_buckets=32, guard_loss=False):
-        """max_buckets: the least recently used bucket (its graphs and buffers) is dropped beyond it."""
+    lossf a DirectDepthLoss (a depth-head conf): the bucket also carries the scenes' per-edge depth
+    targets, and with ``two_view_error`` their ground-truth cameras and fresh pairing keys; the step
+    runs batch_depth_loss and the errors are batch_depth_errors' 2-view error per scene."""
+
+    def __init__(self, net, lossf, warmup=2, optimizer=None, max_buckets=32, guard_loss=False, two_view_error=False):
+        """max_buckets: the least recently used bucket (its graphs and buffers) is dropped beyond it.
+        two_view_error (DirectDepthLoss only): the per-scene errors are the 2-view error of the depth
+        head (repro_backproj_rnd_gt_2view, needs every scene's ``y``); without it they are NaN."""
         require_gasfm(net, "StaticTrainer")
         self.net, self.lossf = net, lossf
+        self.depth = isinstance(lossf, DirectDepthLoss)
+        if two_view_error and not self.depth:
+            raise ValueError("StaticTrainer: two_view_error is the depth head's metric (DirectDepthLoss)")
+        self.two_view_error = two_view_error
         self.max_buckets = max_buckets
         self.optimizer = optimizer
         self.guard_loss = guard_loss
@@ -664,8 +794,22 @@ class StaticTrainer:
         preds = union.split(self.net(union))
         loss = sum(self.lossf(p, d) for p, d in zip(preds, datas))
         loss.backward()
-        errs = [float(evaluation.reprojection_error_mean(d, p)) for p, d in zip(preds, datas)]
+        if not self.depth:
+            errs = [float(evaluation.reprojection_error_mean(d, p)) for p, d in zip(preds, datas)]
+        elif self.two_view_error:  # compute_core_errors' repro_backproj_rnd_gt_2view per scene
+            tots = [evaluation.backproj_2view_error(d, *evaluation._depth_pair(d, p))[0] for p, d in zip(preds, datas)]
+            errs = [float(t[0] / t[1]) for t in tots]
+        else:
+            errs = [float("nan")] * len(datas)
         return loss.detach(), errs
+
+    def _check_depth_scenes(self, datas):
+        for i, d in enumerate(datas):
+            name = getattr(d, "scene_name", i)
+            if getattr(d, "depths", None) is None:
+                raise ValueError(f"StaticTrainer: scene '{name}' carries no depths (DirectDepthLoss)")
+            if self.two_view_error and getattr(d, "y", None) is None:
+                raise ValueError(f"StaticTrainer: scene '{name}' carries no ground-truth cameras y (two_view_error)")
 
     @property
     def grad_norm(self):
@@ -716,6 +860,8 @@ class StaticTrainer:
         converts it)."""
         from .graph_step import CapturedStep
         inputs = datas if inputs is None else inputs
+        if self.depth:
+            self._check_depth_scenes(datas)
         self._tick(None)
         st = BatchStats(inputs) if stats is None else stats
         why = st.expressible()
@@ -731,6 +877,8 @@ class StaticTrainer:
         dev = inputs[0].x.values.device
         b, _ = self._bucket(st, dev)
         sb = b[0]
+        if self.depth:
+            sb.enable_depth()
         self._tick("stats")
         sb.fill(datas, st, inputs)
         self._tick("fill")
@@ -738,8 +886,12 @@ class StaticTrainer:
 
         def fwd_bwd():
             pred = self.net(sb)
-            loss = batch_loss(pred, sb, self.lossf)
-            out["err"] = batch_repro_errors(pred, sb)
+            if self.depth:
+                loss = batch_depth_loss(pred, sb, self.lossf)
+                out["err"] = batch_depth_errors(pred, sb) if self.two_view_error else sb.zero_err
+            else:
+                loss = batch_loss(pred, sb, self.lossf)
+                out["err"] = batch_repro_errors(pred, sb)
             loss.backward()
             return loss
 
