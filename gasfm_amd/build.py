@@ -17,6 +17,7 @@ HEADER = os.path.join(HERE, "..", "include", "gasfm.h")  # the C ABI; gasfm_amd/
 DEPTH_HEAD_HEADER = os.path.join(HERE, "..", "include", "gasfm_depth_head.h")  # read by gasfm_amd/depth_head/_binding.py
 DEPTH_EVAL_HEADER = os.path.join(HERE, "..", "include", "gasfm_depth_eval.h")  # read by gasfm_amd/depth_eval/_binding.py
 DEPTH_BATCH_HEADER = os.path.join(HERE, "..", "include", "gasfm_depth_batch.h")  # read by gasfm_amd/depth_batch/_binding.py
+EDGE_WIDE_HEADER = os.path.join(HERE, "..", "include", "gasfm_edge_wide.h")  # read by gasfm_amd/edge_wide/_binding.py
 ARCH = os.environ.get("GASFM_OFFLOAD_ARCH", "gfx950")
 
 
@@ -38,7 +39,7 @@ def _stale():
         return True
     t = os.path.getmtime(LIB)
     deps = sources() + glob.glob(os.path.join(CSRC, "*.hpp")) + [HEADER, DEPTH_HEAD_HEADER, DEPTH_EVAL_HEADER,
-                                                                          DEPTH_BATCH_HEADER]
+                                                                          DEPTH_BATCH_HEADER, EDGE_WIDE_HEADER]
     return any(os.path.getmtime(p) > t for p in deps if os.path.exists(p))
 
 

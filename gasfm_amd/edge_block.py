@@ -25,7 +25,7 @@ from collections import namedtuple
 
 import torch
 
-from . import _native
+from . import _native, edge_wide
 from .attention import (attn_backward_raw, attn_forward_partial, attn_forward_raw, bwd_combine, bwd_combine2,
                         combine_fwd_l1, combine_partials)
 
@@ -616,6 +616,68 @@ def _epilogue0_backward(ctx, saved, dPo, bnd=None):
     return (None, aux, dSp, dSv, dSg.view(ctx.sg_shape), tot[:64].view(32, 2),
             _bias_grad(dSv, dSg, getattr(ctx, "defer_b", False), shared=bnd is not None), None, None,
             tot[160:162], tot[162:164], tot[64:128].view(32, 2), tot[128:160], None, None)
+
+
+class WideEpilogueFn(torch.autograd.Function):
+    """The edge epilogue of a depth conf's last block (32-wide P in, 128-wide P' out; csrc/edge_wide.hip):
+
+        P' = Wsk relu(LN_b(P)) + bsk + (Wp [relu(LN_a(P)) | P0] + bp + Sp[pt] + Sv[cam] + Sg) / 4
+
+    Self-contained: its backward returns this epilogue's whole dP (both LayerNorm backwards), which
+    autograd adds to the dP of the block's attention half (EdgeCamFn run with no token gradient), and
+    LN_a's parameter gradients likewise add to those EdgeCamFn returns.  Wp [128, 34] with P0 [E, 2],
+    [128, 32] without; Sp [n, 128], Sv [m, 128] rows, Sg 128 values."""
+
+    @staticmethod
+    def forward(ctx, P, P0, Sp, Sv, Sg, Wp, bp, Wsk, bsk, lna_w, lna_b, lnb_w, lnb_b, eps, edges):
+        P = P.contiguous()
+        P0 = P0.contiguous() if P0 is not None else None
+        Wp_c, Wsk_c = Wp.contiguous(), Wsk.contiguous()
+        out = torch.empty((P.shape[0], Wp.shape[0]), dtype=torch.float32, device=P.device)
+        edge_wide.epilogue_fwd(P, P0, edges.cam, edges.pt, lna_w, lna_b, lnb_w, lnb_b, eps, Wp_c,
+                                       bp.contiguous(), Wsk_c, bsk.contiguous(), Sp.contiguous(), _rows(Sv),
+                                       Sg.reshape(-1).contiguous(), PROJ_SCALE, out)
+        ctx.eps, ctx.edges, ctx.sg_shape = eps, edges, Sg.shape
+        # LN_a also receives EdgeCamFn's sum in the same pass: the deferral fills the first and sums
+        # the second at once (_native.param_colsum's repeated-target path)
+        ctx.defer = _native.defer_token(Wp, Wsk, bsk, lna_w, lna_b, lnb_w, lnb_b)
+        ctx.defer_b = _native.defer_token(bp)
+        ctx.save_for_backward(P, P0, Wp_c, Wsk_c, lna_w, lna_b, lnb_w, lnb_b)
+        return out
+
+    @staticmethod
+    def backward(ctx, dPo):
+        P, P0, Wp, Wsk, lna_w, lna_b, lnb_w, lnb_b = ctx.saved_tensors
+        edges, dev, E = ctx.edges, P.device, P.shape[0]
+        pc, pp = edges.plans["proj2view"], edges.plans["proj2scenepoint"]
+        W, ldWp = Wp.shape[0], Wp.shape[1]
+        if E == 0 or pc.n_items == 0:  # no edge, no launch: every sum is empty
+            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+            return (z(E, 32), z(E, 2) if P0 is not None else None, z(edges.n, W), z(edges.m, W), z(W).view(ctx.sg_shape),
+                    torch.zeros_like(Wp), z(W), torch.zeros_like(Wsk), z(W), z(32), z(32), z(32), z(32), None, None)
+        dPo = dPo.contiguous()
+        dP = torch.empty_like(P)
+        dP0 = torch.empty((E, 2), dtype=torch.float32, device=dev) if P0 is not None else None
+        # camera side: dP, dP0, dSv and the parameter partials in one pass over the camera work items
+        dSv = torch.empty((edges.m, W), dtype=torch.float32, device=dev)
+        part_dsv = torch.empty((max(pc.n_part_rows, 1), W), dtype=torch.float32, device=dev)
+        part = torch.empty(edge_wide.part_shape(1, E, pc.n_items, ldWp), dtype=torch.float32, device=dev)
+        edge_wide.epilogue_bwd(pc.items, pc.n_items, dPo, P, P0, lna_w, lna_b, lnb_w, lnb_b, ctx.eps, Wp, Wsk,
+                                       PROJ_SCALE, dP, dP0, dSv, part_dsv, part)
+        bwd_combine(pc, part_dsv, W, dSv)
+        tot = _native.param_colsum(part, ctx.defer)
+        dSg = _native.colsum(dSv)  # == d bias_proj: every edge belongs to one camera
+        # point side: dSp = per-point sum of dP'/4 through the point permutation
+        dSp = torch.empty((edges.n, W), dtype=torch.float32, device=dev)
+        part_dsp = torch.empty((max(pp.n_part_rows, 1), W), dtype=torch.float32, device=dev)
+        edge_wide.segment_rowsum_w(pp.items, pp.n_items, pp.perm, dPo, PROJ_SCALE, dSp, part_dsp)
+        bwd_combine(pp, part_dsp, W, dSp)
+        o1 = W * ldWp
+        o2 = o1 + W * 32
+        o3 = o2 + W
+        return (dP, dP0, dSp, dSv, dSg.view(ctx.sg_shape), tot[:o1].view(W, ldWp), _bias_grad(dSv, dSg, ctx.defer_b),
+                tot[o1:o2].view(W, 32), tot[o2:o3], tot[o3:o3 + 32], tot[o3 + 32:o3 + 64], tot[o3 + 64:o3 + 96],
+                tot[o3 + 96:o3 + 128], None, None)
 
 
 class Seam0Fn(torch.autograd.Function):

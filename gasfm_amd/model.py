@@ -30,7 +30,7 @@ from . import _native, dense, edge_block, edge_ops, point_block, view_block
 from . import depth_head as depth_head_op
 from .attention import AttnPlan, GatAttentionFn, gat_attention
 from .edge_block import (Block0PrologueFn, CamArgs, DualAttentionFn, EdgeCamFn, EdgePrologueFn, Epilogue0Args,
-                         EpilogueArgs, PendingEpilogue, materialize)
+                         EpilogueArgs, PendingEpilogue, WideEpilogueFn, materialize)
 from .gatv2 import GATv2Conv, zero_target_rows
 
 
@@ -42,6 +42,10 @@ EDGE_CAM = os.environ.get("GASFM_EDGE_CAM", "1") != "0"
 EDGE_SEAM = os.environ.get("GASFM_EDGE_SEAM", "1") != "0"
 # Block 0's (2-wide) epilogue likewise inside block 1's prologue kernel (Seam0Fn, gasfm_edge0_seam_fwd).
 EDGE_SEAM0 = os.environ.get("GASFM_EDGE_SEAM0", "1") != "0"
+# A depth conf's last block (32-wide features in, 128-wide out: lin_proj [128, 34], LayerNorm'd skip
+# projection [128, 32]) on the fused edge kernels (forward_fused_wide, csrc/edge_wide.hip);
+# GASFM_EDGE_WIDE=0: the unfused aten route.
+EDGE_WIDE = os.environ.get("GASFM_EDGE_WIDE", "1") != "0"
 # A block's whole global-node chain (its tail and every consumer of g) as one GlobalChainFn
 # (csrc/global_chain.hip, round 4); GASFM_GLOBAL_CHAIN=0: the GlobalLinearFn / GlobalHubFn path.
 GLOBAL_CHAIN = os.environ.get("GASFM_GLOBAL_CHAIN", "1") != "0"
@@ -700,6 +704,8 @@ class GraphAttnSfMLayer(Module):
                 self.residual_skipconn_proj_norm_layer = LayerNorm(n_feat_proj_in)
             self.skip_projection = ProjLayer(n_feat_proj_in, n_feat_proj_out)
 
+    last_route = None  # the route the last forward_plan took: "fused", "fused0", "wide" or "unfused"
+
     def fusable(self):
         pfu = self.projection_feature_update
         w = pfu.lin_proj.weight
@@ -719,6 +725,44 @@ class GraphAttnSfMLayer(Module):
                 and tuple(w.shape) == (32, 2) and tuple(self.skip_projection.lin_proj.weight.shape) == (32, 2)
                 and self.prev_projfeat_norm_layer.normalized_shape == (2,)
                 and self.global_feature_update.fusable0())
+
+    def fusable_wide(self):
+        """The 32 -> 128 last block of a depth conf: LayerNorm and residual on, the LayerNorm'd skip
+        projection [128, 32], lin_proj [128, 34] (init-feature skip) or [128, 32], no hidden layers."""
+        pfu = self.projection_feature_update
+        w = pfu.lin_proj.weight
+        if not (self.use_norm_proj_update and self.add_residual_skipconn_proj_update
+                and self.skip_projection is not None):
+            return False
+        la, lb, sk = self.prev_projfeat_norm_layer, self.residual_skipconn_proj_norm_layer, self.skip_projection.lin_proj
+        return (pfu.n_hidden_layers_proj_update == 0 and pfu.normalize_global_features
+                and tuple(w.shape) in ((128, 34), (128, 32))
+                and (w.shape[1] == 34) == self.add_skipconn_from_init_projfeat
+                and tuple(sk.weight.shape) == (128, 32) and sk.bias is not None and pfu.lin_proj.bias is not None
+                and la.normalized_shape == (32,) and lb.normalized_shape == (32,) and la.eps == lb.eps
+                and la.weight is not None and lb.weight is not None and la.bias is not None and lb.bias is not None
+                and self.global_feature_update.fusable())
+
+    def forward_fused_wide(self, P, plans, edges, prev_pt, prev_view, prev_glob, P0, carry=None):
+        """The 32 -> 128 last block with the fused HIP edge kernels: the attention half as forward_fused
+        (EdgeCamFn without the lin_proj gradient or a token gradient; a PendingEpilogue P runs in its
+        kernel, SeamFn), then edge_block.WideEpilogueFn.  Returns the materialised P' [E, 128]."""
+        la, lb = self.prev_projfeat_norm_layer, self.residual_skipconn_proj_norm_layer
+        gfu, pfu = self.global_feature_update, self.projection_feature_update
+        P0e = P0 if self.add_skipconn_from_init_projfeat else None
+        if gfu.cam_fusable(plans):
+            attend = EdgeCamAttend(gfu, P, la.weight, la.bias, la.eps, None, plans)
+            pts, view, glob = gfu.forward_fused(None, plans, prev_pt, prev_view, prev_glob, carry, attend=attend)
+            P = attend.P
+        else:
+            P = materialize(P)
+            XL, _ = gfu.prologue(P, plans, la)
+            pts, view, glob = gfu.forward_fused(XL, plans, prev_pt, prev_view, prev_glob, carry)
+        sp, sv, sg = _edge_terms(pfu, pts, view, glob, plans, carry)
+        sk = self.skip_projection.lin_proj
+        Pn = WideEpilogueFn.apply(P, P0e, sp, sv, sg, pfu.lin_proj.weight, pfu.lin_proj.bias, sk.weight, sk.bias,
+                                  la.weight, la.bias, lb.weight, lb.bias, la.eps, edges)
+        return Pn, pts, view, glob
 
     def forward_fused0(self, P, plans, edges, carry=None, nxt=None):
         """Block 0 (2-wide inputs, projected residual) with the block-0 HIP edge kernels."""
@@ -767,10 +811,18 @@ class GraphAttnSfMLayer(Module):
         carry / nxt: see GraphAttnSfMGlobalFeatureUpdate.forward_fused (fused CUDA path only).  On
         the fused path P and P' may be PendingEpilogue handles (edge_block.SeamFn)."""
         if (isinstance(P, PendingEpilogue) or P.is_cuda) and self.fusable():
+            self.last_route = "fused"
             return self.forward_fused(P, plans, edges, prev_pt, prev_view, prev_glob, P0, carry, nxt)
+        if EDGE_WIDE and plans.get("_shard") is None and self.fusable_wide() \
+                and (isinstance(P, PendingEpilogue)
+                     or (P.is_cuda and P.dtype == torch.float32 and P.dim() == 2 and P.shape[1] == 32)):
+            self.last_route = "wide"
+            return self.forward_fused_wide(P, plans, edges, prev_pt, prev_view, prev_glob, P0, carry)
         P = materialize(P)
         if P.is_cuda and prev_pt is None and prev_view is None and prev_glob is None and self.fusable0():
+            self.last_route = "fused0"
             return self.forward_fused0(P, plans, edges, carry, nxt)
+        self.last_route = "unfused"
         if carry is not None and carry.pending():
             raise RuntimeError("point hub outputs pending for a block on the unfused path")
         if self.use_norm_proj_update:
@@ -1084,6 +1136,7 @@ class GraphAttnSfMNet(BaseNet):
         return scene_edge_index(data, device)
 
     last_carry = None  # the last forward's BlockCarry: the tests read that nothing stays pending in it
+    last_routes = ()  # the route each block of the last forward took (GraphAttnSfMLayer.last_route)
 
     def forward_features(self, values, edges):
         """Block stack + final update on raw tensors; returns (P, pts, view) after the final update."""
@@ -1113,6 +1166,7 @@ class GraphAttnSfMNet(BaseNet):
                 nxt = fgu if final_fused else None
             prev = (pts, view, glob) if sf else (None, None, None)
             P, pts, view, glob = blk.forward_plan(P, plans, edges, *prev, P0=p0s[i], carry=carry, nxt=nxt)
+        self.last_routes = tuple(blk.last_route for blk in blocks)
         if heads:
             args = (pts, view, glob) if sf else (None, None, None)
             pend = isinstance(P, PendingEpilogue)
